@@ -9,8 +9,12 @@
     python bench.py --gpus N ...            # no launcher: spawns the N rank processes itself (before any GPU call)
     python bench.py --gpus N --scaling strong   # global batch 128 split over the ranks (default: weak, 128 per GPU)
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline     -- the dominant MFMA kernel: algorithmic FLOPs / HIP-event duration, measured live
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step).
+A plain run does only what that line needs: set-up, warm-up, the timed steps and, with --dump-outputs DIR, the
+outputs of the last timed step.  --full adds, after the timed region:
+  roofline     -- the dominant MFMA kernel: algorithmic FLOPs / HIP-event duration, measured live (two extra steps)
+  strong       -- N > 1: the step at the per-rank batch of a strong-scaling run
+  parity_path  -- the split-bf16 and float32 parity paths timed on the same step
   cpu_baseline -- the CPU oracle (a port of the reference's PyTorch CPU path) timed on this host
 """
 import argparse
@@ -79,7 +83,18 @@ def parse():
                     "128 split over the ranks; eager launches unless --graph on / multi) that follows the timed weak-scaling steps")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-iters", type=int, default=4, help="timed CPU iterations (about 10 s of host work in total)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the roofline leg, the strong-scaling "
+                    "leg (N > 1), the parity paths and the CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy "
+                    "(float32; arrays above 2M elements as a fixed, seeded sample of 2M of them)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.gemm_table and not args.full:
+        ap.error("--gemm-table is written by the roofline leg: add --full")
+    return args
 
 
 def synthetic_batch(B, H, W, nb_cls, N, seed=0):
@@ -93,6 +108,26 @@ def synthetic_batch(B, H, W, nb_cls, N, seed=0):
     lengths = rng.integers(lo, hi, size=B).astype(np.int32)
     targets = rng.integers(1, nb_cls, size=int(lengths.sum())).astype(np.int32)
     return x, targets, lengths
+
+
+DUMP_SAMPLE = 1 << 21       # elements kept of a larger array: 8 MB each, so that every dump stays far below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: device / host tensor} -> out_dir/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is
+    written as the elements at DUMP_SAMPLE fixed positions (seeded, sorted) of its flattened form, so that two builds
+    run with the same arguments compare position for position."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            out = flat.float().cpu().numpy()
+        else:
+            out = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, f"{name}.npy"), out)
 
 
 def cpu_baseline(args, mask):
@@ -334,10 +369,13 @@ def main():
         eng = model._engine(dev)
         set_stem_fusion(eng, args)
         P = dict(model.state_dict(keep_vars=True))
+        last_logits = []
 
         def one_step():
             y = eng.forward(P, x, train=False, save=False)
             nll, _ = ctc_forward_backward(y, tg, tl, want_grad=False)
+            if args.dump_outputs:
+                last_logits[:] = [y]
             return nll
     else:
         model.train()
@@ -403,75 +441,89 @@ def main():
     ms = dt / args.steps * 1e3
     value = B * world * args.steps / dt
 
+    # ---- what the last timed step computed, before any step below changes the weights ----
+    if args.dump_outputs and rank == 0:
+        if args.forward_only:
+            outs = {"logits": last_logits[0], "nll": loss}
+        else:      # what a caller of the training step holds afterwards: its loss, the updated weights and buffers, the gradients
+            named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+            outs = {"loss": loss, "params": torch.cat([p.detach().reshape(-1) for _, p in named]),
+                    "grads": torch.cat([tr.flat.G[n].reshape(-1) for n, _ in named]),
+                    "buffers": torch.cat([b.reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()])}
+        dump_outputs(args.dump_outputs, outs)
+        del outs
+
     # ---- strong-scaling leg (N > 1, after the timed weak-scaling steps; not part of `value`): the global batch of 128
     # split over the ranks -- SURVEY.md 8(d) asks for both curves, the driver's one command records both ----
     strong = None
-    if world > 1 and args.scaling == "weak" and not (args.forward_only or args.sam or args.no_strong_leg) and args.batch % world == 0:
+    full_train = args.full and args.scaling == "weak" and not (args.forward_only or args.sam)
+    if full_train and world > 1 and not args.no_strong_leg and args.batch % world == 0:
         strong = strong_leg(args, dev, world, rank, dtype, use_dist)
-    elif world == 1 and args.scaling == "weak" and not (args.forward_only or args.sam):
+    elif full_train and world == 1:
         strong = {"global_batch": B, "batch_per_gpu": B, "ms_per_step": round(ms, 3), "value": round(value, 1),
                   "unit": "line-images/s", "note": "one GPU: the strong- and the weak-scaling step are the same step"}
 
     # ---- roofline leg: HIP events around every MFMA launch of two extra steps (not part of `value`) ----
     roof = None
-    # every rank runs the two extra steps (they contain collectives); only rank 0 records events
-    if rank == 0:
-        ops.PROFILE = {}
-    if not args.forward_only:
-        saved_overlap, tr.engine.overlap_wgrad = tr.engine.overlap_wgrad, False   # one stream: events time ONE kernel
-    # (a replayed graph has no per-launch events: the two profiled steps always run as eager launches)
-    prof_step = one_step if (args.forward_only or args.sam or args.graph == "off") else (lambda: tr.step(x, tg, tl, keep_mask=keep))
-    for _ in range(2):
-        prof_step()
-    torch.cuda.synchronize()
-    if not args.forward_only:
-        tr.engine.overlap_wgrad = saved_overlap
-    if rank == 0:
-        prof, ops.PROFILE = ops.PROFILE, None
-        rows, by_sym = [], {}
-        for key, ent in prof.items():
-            ts = [a.elapsed_time(b) for a, b in ent["events"]]
-            rows.append((sum(ts), key, ent["flops"], sum(ts) / len(ts), len(ts) // 2, ent["kernel"]))
-            sym = by_sym.setdefault(ent["kernel"], {"ms": 0.0, "flops": 0.0, "n": 0, "shapes": []})
-            sym["ms"] += sum(ts)
-            sym["flops"] += ent["flops"] * len(ts)
-            sym["n"] += len(ts)
-            sym["shapes"].append((sum(ts), key, ent["flops"], sum(ts) / len(ts), len(ts) // 2))
-        rows.sort(reverse=True)
-        names = {0: "plain", 1: "conv-fwd", 2: "conv-dgrad", 3: "conv-wgrad"}
-        if args.gemm_table:
-            with open(args.gemm_table, "w") as f:
-                f.write("ms/step  avg_us  n/step  TFLOP/s  kernel | dtype,aL,bL,gather,M,N,K,batch\n")
-                for t_, k_, fl_, av_, n_, sy_ in rows:
-                    f.write(f"{t_ / 2:7.3f} {av_ * 1e3:8.1f} {n_:4d} {fl_ / (av_ * 1e-3) / 1e12:8.1f}  {sy_} | {k_}\n")
-        # dominant kernel = the rocprofv3 SYMBOL with the largest time share (one symbol serves several launch shapes);
-        # achieved = its algorithmic FLOPs per launch / its average launch duration, both averaged over all its launches
-        # of a step, which is what the `rocprofv3 --kernel-trace --stats` row of that symbol averages too
-        symname, sym = max(by_sym.items(), key=lambda kv: kv[1]["ms"])
-        avg_ms = sym["ms"] / sym["n"]
-        flops = sym["flops"] / sym["n"]
-        per_step = sym["n"] // 2
-        achieved = flops / (avg_ms * 1e-3) / 1e12
-        sym["shapes"].sort(reverse=True)
-        shapes = [{"shape": f"{names[k_[3]]} M={k_[4]} N={k_[5]} K={k_[6]} batch={k_[7]}", "launches_per_step": n_,
-                   "avg_ms": round(av_, 4), "tflops": round(fl_ / (av_ * 1e-3) / 1e12, 1)} for _, k_, fl_, av_, n_ in sym["shapes"][:4]]
-        traffic, traffic_src = None, None
-        try:   # HBM bytes per launch (mean over the symbol's launches) from the newest committed PMC passes
-            tj = args.traffic_json or newest_traffic_json()
-            with open(tj) as f:
-                pm = json.load(f)
-            ent = pm["symbols"].get(symname)
-            if ent is not None and B == 128 and args.width == 1024 and args.dtype == "bf16" and not args.forward_only:
-                traffic, traffic_src = ent["traffic_bytes_per_launch_mean"], os.path.relpath(tj, ROOT)
-        except (OSError, KeyError, ValueError, TypeError):
-            pass
-        roof = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s",
-                "frac": round(achieved / PEAK_TFLOPS[args.dtype], 4), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": symname, "launches_per_step": per_step, "avg_ms": round(avg_ms, 4),
-                "algorithmic_gflop_per_launch": round(flops / 1e9, 1), "ms_per_step": round(sym["ms"] / 2, 3),
-                "top_shapes": shapes,
-                "mfma_ms_per_step": round(sum(r[0] for r in rows) / 2, 2),
-                "all_mfma_tflops": round(sum(r[2] * len(prof[r[1]]["events"]) for r in rows) / sum(r[0] for r in rows) / 1e9, 1)}
+    if args.full:
+        # every rank runs the two extra steps (they contain collectives); only rank 0 records events
+        if rank == 0:
+            ops.PROFILE = {}
+        if not args.forward_only:
+            saved_overlap, tr.engine.overlap_wgrad = tr.engine.overlap_wgrad, False   # one stream: events time ONE kernel
+        # (a replayed graph has no per-launch events: the two profiled steps always run as eager launches)
+        prof_step = one_step if (args.forward_only or args.sam or args.graph == "off") else (lambda: tr.step(x, tg, tl, keep_mask=keep))
+        for _ in range(2):
+            prof_step()
+        torch.cuda.synchronize()
+        if not args.forward_only:
+            tr.engine.overlap_wgrad = saved_overlap
+        if rank == 0:
+            prof, ops.PROFILE = ops.PROFILE, None
+            rows, by_sym = [], {}
+            for key, ent in prof.items():
+                ts = [a.elapsed_time(b) for a, b in ent["events"]]
+                rows.append((sum(ts), key, ent["flops"], sum(ts) / len(ts), len(ts) // 2, ent["kernel"]))
+                sym = by_sym.setdefault(ent["kernel"], {"ms": 0.0, "flops": 0.0, "n": 0, "shapes": []})
+                sym["ms"] += sum(ts)
+                sym["flops"] += ent["flops"] * len(ts)
+                sym["n"] += len(ts)
+                sym["shapes"].append((sum(ts), key, ent["flops"], sum(ts) / len(ts), len(ts) // 2))
+            rows.sort(reverse=True)
+            names = {0: "plain", 1: "conv-fwd", 2: "conv-dgrad", 3: "conv-wgrad"}
+            if args.gemm_table:
+                with open(args.gemm_table, "w") as f:
+                    f.write("ms/step  avg_us  n/step  TFLOP/s  kernel | dtype,aL,bL,gather,M,N,K,batch\n")
+                    for t_, k_, fl_, av_, n_, sy_ in rows:
+                        f.write(f"{t_ / 2:7.3f} {av_ * 1e3:8.1f} {n_:4d} {fl_ / (av_ * 1e-3) / 1e12:8.1f}  {sy_} | {k_}\n")
+            # dominant kernel = the rocprofv3 SYMBOL with the largest time share (one symbol serves several launch shapes);
+            # achieved = its algorithmic FLOPs per launch / its average launch duration, both averaged over all its launches
+            # of a step, which is what the `rocprofv3 --kernel-trace --stats` row of that symbol averages too
+            symname, sym = max(by_sym.items(), key=lambda kv: kv[1]["ms"])
+            avg_ms = sym["ms"] / sym["n"]
+            flops = sym["flops"] / sym["n"]
+            per_step = sym["n"] // 2
+            achieved = flops / (avg_ms * 1e-3) / 1e12
+            sym["shapes"].sort(reverse=True)
+            shapes = [{"shape": f"{names[k_[3]]} M={k_[4]} N={k_[5]} K={k_[6]} batch={k_[7]}", "launches_per_step": n_,
+                       "avg_ms": round(av_, 4), "tflops": round(fl_ / (av_ * 1e-3) / 1e12, 1)} for _, k_, fl_, av_, n_ in sym["shapes"][:4]]
+            traffic, traffic_src = None, None
+            try:   # HBM bytes per launch (mean over the symbol's launches) from the newest committed PMC passes
+                tj = args.traffic_json or newest_traffic_json()
+                with open(tj) as f:
+                    pm = json.load(f)
+                ent = pm["symbols"].get(symname)
+                if ent is not None and B == 128 and args.width == 1024 and args.dtype == "bf16" and not args.forward_only:
+                    traffic, traffic_src = ent["traffic_bytes_per_launch_mean"], os.path.relpath(tj, ROOT)
+            except (OSError, KeyError, ValueError, TypeError):
+                pass
+            roof = {"bound": "mfma", "achieved": round(achieved, 1), "peak": PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s",
+                    "frac": round(achieved / PEAK_TFLOPS[args.dtype], 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "kernel": symname, "launches_per_step": per_step, "avg_ms": round(avg_ms, 4),
+                    "algorithmic_gflop_per_launch": round(flops / 1e9, 1), "ms_per_step": round(sym["ms"] / 2, 3),
+                    "top_shapes": shapes,
+                    "mfma_ms_per_step": round(sum(r[0] for r in rows) / 2, 2),
+                    "all_mfma_tflops": round(sum(r[2] * len(prof[r[1]]["events"]) for r in rows) / sum(r[0] for r in rows) / 1e9, 1)}
 
     if rank == 0:
         model_tag = f"d{args.embed_dim}/{args.depth}L/{args.heads}h, nb_cls {args.nb_cls}"
@@ -497,10 +549,10 @@ def main():
             out["config"]["collective_backend"] = "rccl" if args.backend == "nccl" else "gloo (ranks share a GPU: a rehearsal of the control flow, not a measurement)"
         if strong is not None:
             out["strong"] = strong
-        if (not args.no_parity_path and world == 1 and args.dtype == "bf16" and not args.forward_only and not args.sam
+        if (args.full and not args.no_parity_path and world == 1 and args.dtype == "bf16" and not args.forward_only and not args.sam
                 and args.scaling == "weak"):
             out["parity_path"] = parity_path(args, dev, x, tg, tl, keep)
-        if not args.no_cpu_baseline:     # rank 0, after the timed region (N > 1: the other ranks wait at the closing barrier)
+        if args.full and not args.no_cpu_baseline:     # rank 0, after the timed region (N > 1: the other ranks wait at the closing barrier)
             out["cpu_baseline"] = cpu_baseline(args, keep)
         print(json.dumps(out), flush=True)
     if use_dist:

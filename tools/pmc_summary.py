@@ -80,12 +80,12 @@ def main():
                       1024.0 * sum(ws) / max(1, len(ws)) / 1e6, busy / (gui / 8.0 * 1024) if gui else None, gui / 8.0 / max(1, len(fs))))
     grows.sort(key=lambda r: -(r[6] * r[2]))
     with open(a.dst + "_traffic.json", "w") as f:
-        json.dump({"source": "tools/collect_pmc.sh (rocprofv3 --pmc, separate passes) over bench.py --steps 1 --warmup 1 "
+        json.dump({"source": "tools/collect_pmc.sh (rocprofv3 --pmc, separate passes) over bench.py --full --steps 1 --warmup 1 "
                              "--no-overlap-wgrad; read bytes = 2 x FETCH_SIZE KiB x 1024, written = WRITE_SIZE KiB x 1024",
                    "symbols": symbols}, f, indent=1)
     with open(a.dst + ".md", "w") as o:
         o.write("# Hardware counters per kernel symbol, one training step (bf16, B=128, 64x1024)\n\n")
-        o.write("`tools/collect_pmc.sh` = four `rocprofv3 --pmc ... --kernel-trace` passes over `python3 bench.py --steps 1 --warmup 1 "
+        o.write("`tools/collect_pmc.sh` = four `rocprofv3 --pmc ... --kernel-trace` passes over `python3 bench.py --full --steps 1 --warmup 1 "
                 "--no-cpu-baseline --no-overlap-wgrad`; averages per launch over all launches of a symbol.  Durations are from the "
                 "FETCH_SIZE pass (counter collection serialises dispatches; see the kernel-trace profile for timings).\n\n")
         o.write("| kernel | launches/step | avg us | HBM read MB | HBM written MB | MFMA busy | LDS conflict cycles / LDS cycles | wave wait share |\n")

@@ -11,7 +11,7 @@ cd $ROOT
 for rep in 1 2 3; do
   for mode in new old; do
     if [ $mode = old ]; then export HTRVT_NO_PERSISTENT_GEMM=1 HTRVT_NO_MNMAJOR_8PHASE=1 HTRVT_ENGINE_OVERRIDE="relu_bitmask=0"; else unset HTRVT_NO_PERSISTENT_GEMM HTRVT_NO_MNMAJOR_8PHASE HTRVT_ENGINE_OVERRIDE; fi
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-path > $O/ab_${mode}_$rep.json 2> $O/ab_${mode}_$rep.err
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-path > $O/ab_${mode}_$rep.json 2> $O/ab_${mode}_$rep.err
     python - $O/ab_${mode}_$rep.json $mode $rep >> $O/ab.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
