@@ -106,6 +106,10 @@ PROTOTYPES = {
     "htrvt_relayout_host": (i32, [vp, i32, i32, i32, vp]),
     "htrvt_relpos_bias_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "htrvt_relpos_bias_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "htrvt_attn_relpos_supported": (i32, [i32, i32, i32, i32, i32, i32]),
+    "htrvt_attn_relpos_bwd_workspace_floats": (i64, [i32, i32, i32, i32, i32, i32]),
+    "htrvt_attn_relpos_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]),
+    "htrvt_attn_relpos_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp]),
     "htrvt_cast_transpose_f32": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "htrvt_split_bf16": (i32, [vp, i64, i32, i64, vp, i32, i32, i32, vp, vp, vp]),
     "htrvt_elementwise_f32": (i32, [vp, vp, vp, i64, i32, vp]),

@@ -28,11 +28,35 @@ BN_EPS = 1e-5       # resnet18.py:16
 BN_MOMENTUM = 0.1
 
 
+def _pool_len(n, k, s, p):
+    return (n + 2 * p - k) // s + 1
+
+
+def stem_tokens(H, W):
+    """tokens the ResNet18 stem leaves for an H x W image (resnet18.py:73-84: conv1 s(2,1), max-pool 3 s(2,1) p1,
+    layer1 s(2,1), layer2 / layer3 s2, max-pool 3 s(2,1) p1)"""
+    h, w = _pool_len(H, 3, 2, 1), W
+    h, w = _pool_len(h, 3, 2, 1), _pool_len(w, 3, 1, 1)
+    h, w = _pool_len(h, 3, 2, 1), w
+    h, w = _pool_len(h, 3, 2, 1), _pool_len(w, 3, 2, 1)
+    h, w = _pool_len(h, 3, 2, 1), _pool_len(w, 3, 2, 1)
+    h, w = _pool_len(h, 3, 2, 1), _pool_len(w, 3, 1, 1)
+    return h * w
+
+
 class ModelShape:
     """Static shape of one model (mirrors MaskedAutoencoderViT.__init__, HTR_VT.py:143-172)."""
 
-    def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS):
+    def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS,
+                 pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False):
+        """The switches of the window-attention fork (model_window/model/HTR_VT.py), defaults = model_v1:
+        pos_embed: tokens get the absolute position embedding; whiten_logits: the parameter-free LayerNorm over the logits;
+        relpos: None, or per block (window, shift) -- attention with the block's relative-position table
+        `blocks.{i}.attn.relative_position_bias_table` [2 table_patches - 1, heads] (window 0: full attention);
+        dropout: the model has dropout / drop-path in train mode (not implemented: a train-mode forward is refused)."""
         self.nb_cls = int(nb_cls)
+        self.pos_embed, self.whiten_logits, self.dropout = bool(pos_embed), bool(whiten_logits), bool(dropout)
+        self.relpos = None if relpos is None else [None if g is None else (int(g[0]), int(g[1])) for g in relpos]
         self.ln_eps = float(ln_eps)
         self.H, self.W = int(img_size[0]), int(img_size[1])
         self.D, self.depth, self.heads = int(embed_dim), int(depth), int(num_heads)
@@ -41,7 +65,14 @@ class ModelShape:
         self.grid = (self.H // patch_size[0], self.W // patch_size[1])
         self.num_patches = self.grid[0] * self.grid[1]
         assert self.D % 32 == 0 and self.D % self.heads == 0
-        assert self.H % 64 == 0 and self.W % 64 == 0, "img_size must be a multiple of 64 (HTR_VT.py:158-160)"
+        if self.relpos is None:
+            assert self.H % 64 == 0 and self.W % 64 == 0, "img_size must be a multiple of 64 (HTR_VT.py:158-160)"
+        else:   # the window fork has no position grid: the token count is what the stem leaves (any W multiple of 8)
+            assert len(self.relpos) == self.depth
+            assert self.H % 64 == 0 and self.W % 8 == 0, "img_size: H a multiple of 64, W of 8"
+            self.num_patches = stem_tokens(self.H, self.W)
+            self.table_patches = int(table_patches if table_patches is not None else self.num_patches)
+            assert self.num_patches <= self.table_patches
 
     def stem_convs(self):
         """(param prefix, Ci, Co, k, stride, pad) of every MFMA conv in execution order (resnet18.py:52-71)."""
@@ -861,6 +892,9 @@ class Engine:
         img: [B,1,H,W] float32.  keep_mask: None or float32 [N] (1 keep / 0 mask-token).
         Returns float32 logits [B,N,nb_cls] (after the final param-free LayerNorm)."""
         s = self.s
+        if train and s.dropout:
+            raise NotImplementedError("train-mode forward of a model with dropout / drop-path: not implemented (build the "
+                                      "window model with create_model(..., dropout=False) to train without them)")
         assert img.is_cuda and img.dtype in (torch.float32, torch.uint8) and img.is_contiguous()
         u8 = 1 if img.dtype == torch.uint8 else 0    # uint8 pixels are read as value / 255 (ToTensor) by the first kernels
         B, _, H, W = img.shape
@@ -1008,7 +1042,12 @@ class Engine:
         assert N == s.num_patches, f"token count {N} != num_patches {s.num_patches}"
         D = s.D
         tok = self._empty(B, N, D)
-        pos = P["pos_embed"].reshape(N, D)
+        if s.pos_embed:
+            pos = P["pos_embed"].reshape(N, D)
+        else:                       # window fork: no absolute position embedding (HTR_VT.py:265 of model_window)
+            if getattr(self, "_zero_pos", None) is None or self._zero_pos.shape != (N, D):
+                self._zero_pos = torch.zeros(N, D, dtype=torch.float32, device=self.dev)
+            pos = self._zero_pos
         check(lib.htrvt_pool_tokens(ptr(x), ptr(keep), ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D, self.dti, st),
               "pool_tokens")
         if save:
@@ -1026,7 +1065,10 @@ class Engine:
             wq, _ = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             qkv = self.linear_fwd(ln1, wq, P[p + ".attn.qkv.bias"])
             O = self._empty(M, D)
-            if self.fused_attention and lib.htrvt_attn_supported(N, hd, self.dti):
+            geo = s.relpos[i] if s.relpos is not None else None
+            if geo is not None:
+                Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st)
+            elif self.fused_attention and lib.htrvt_attn_supported(N, hd, self.dti):
                 # bf16: one launch, scores / probabilities stay on chip; lse2 is what the recomputing backward needs
                 Pm, lse = None, (self._empty(B * h, N, dtype=torch.float32) if save else None)
                 check(lib.htrvt_attn_fwd(ptr(qkv), None, ptr(O), ptr(lse), B, N, h, hd, scale, self.dti, st), "attn_fwd")
@@ -1042,7 +1084,7 @@ class Engine:
             x2 = self.linear_fwd(hact, w2_, P[p + ".mlp.fc2.bias"], residual=x1)
             if save:
                 enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, ln2=ln2, m2=m2, r2=r2,
-                                      hpre=hpre, h=hact))
+                                      hpre=hpre, h=hact, geo=geo))
             xt = x2
 
         # --- norm + head + sequence LayerNorm (HTR_VT.py:236-239) ---
@@ -1050,30 +1092,77 @@ class Engine:
         wh, _ = self._head_w(P["head.weight"])
         raw = self._empty(M, s.nb_cls, dtype=torch.float32)
         gemm(xn, wh, raw, dtype=self.dtype, M=M, N=s.nb_cls, K=D, lda=D, ldb=D, ldc=s.nb_cls, bias=P["head.bias"], c_f32=True)
-        y = self._empty(B, N, s.nb_cls, dtype=torch.float32)
-        sstats = self._empty(B, 2, dtype=torch.float32)
-        check(lib.htrvt_seq_whiten_fwd(ptr(raw), ptr(y), ptr(sstats), B, N * s.nb_cls, WHITEN_EPS, 0, st), "seq_whiten_fwd")
+        if s.whiten_logits:
+            y = self._empty(B, N, s.nb_cls, dtype=torch.float32)
+            sstats = self._empty(B, 2, dtype=torch.float32)
+            check(lib.htrvt_seq_whiten_fwd(ptr(raw), ptr(y), ptr(sstats), B, N * s.nb_cls, WHITEN_EPS, 0, st), "seq_whiten_fwd")
+        else:                       # window fork: head(norm(x)) is the output (no LayerNorm of the logits)
+            y, sstats = raw.view(B, N, s.nb_cls), None
         self._saving = False
         if save:
             sv.update(enc=enc_saved, x_last=xt, xn=xn, mn=mn, rn=rn, y=y, sstats=sstats, B=B, N=N, train=train)
             self.saved = sv
         return y
 
-    def _attention_fwd_unfused(self, qkv, O, B, N, D, h, hd, scale, st):
+    def _relpos_attention_fwd(self, P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st):
+        """attention of a window-fork block with its relative-position table: bf16 on the table-driven fused kernels
+        (csrc/attn_relpos.hip), float32 through the dense bias (htrvt_relpos_bias_fwd) + the unfused GEMM route"""
+        s = self.s
+        ws, shift = geo
+        tab = P[p + ".attn.relative_position_bias_table"]
+        if self.dtype == torch.bfloat16:
+            if not lib.htrvt_attn_relpos_supported(N, hd, self.dti, s.table_patches, ws, shift):
+                raise RuntimeError(f"{p}: relative-position attention: {lib.htrvt_last_error().decode()}")
+            lse = self._empty(B * h, N, dtype=torch.float32) if save else None
+            check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(tab), ptr(O), ptr(lse), B, N, h, hd, scale, s.table_patches, ws, shift,
+                                            self.dti, st), "attn_relpos_fwd")
+            return None, lse
+        assert not self.split, "split_bf16: no relative-position attention"
+        bias = self._empty(h, N, N, dtype=torch.float32)
+        check(lib.htrvt_relpos_bias_fwd(ptr(tab), ptr(bias), N, s.table_patches, ws, shift, h, N, st), "relpos_bias_fwd")
+        return self._attention_fwd_unfused(qkv, O, B, N, D, h, hd, scale, st, bias=bias), None
+
+    def _relpos_attention_bwd(self, P, G, e, dO, dqkv, B, N, D, h, hd, scale, st):
+        """backward of _relpos_attention_fwd; the table gradient is ADDED to G (both routes are reproducible: fixed-order
+        sums, no atomics)"""
+        s = self.s
+        ws, shift = e["geo"]
+        name = e["p"] + ".attn.relative_position_bias_table"
+        tab, gt = P[name], G.get(name)
+        if e["P"] is None:
+            delta = self._empty(B * h, N, dtype=torch.float32)
+            work = None
+            if gt is not None:
+                work = self._empty(lib.htrvt_attn_relpos_bwd_workspace_floats(B, N, h, s.table_patches, ws, shift),
+                                   dtype=torch.float32)
+            check(lib.htrvt_attn_relpos_bwd(ptr(e["qkv"]), ptr(tab), ptr(e["O"]), ptr(dO), ptr(e["lse"]), ptr(delta), ptr(dqkv),
+                                            ptr(gt), ptr(work), B, N, h, hd, scale, s.table_patches, ws, shift, self.dti, st),
+                  "attn_relpos_bwd")
+            return
+        dbias = torch.zeros(h, N, N, dtype=torch.float32, device=self.dev)
+        self._attention_bwd_unfused(e["qkv"], e["P"], dO, dqkv, B, N, D, h, hd, scale, st, dbias=dbias)
+        if gt is not None:
+            dtab = self._empty(*tab.shape, dtype=torch.float32)
+            check(lib.htrvt_relpos_bias_bwd(ptr(dbias), ptr(dtab), N, s.table_patches, ws, shift, h, N, st), "relpos_bias_bwd")
+            check(lib.htrvt_rowsum_f32(ptr(dtab), 1, dtab.numel(), ptr(gt), st), "rowsum")
+
+    def _attention_fwd_unfused(self, qkv, O, B, N, D, h, hd, scale, st, bias=None):
         """float32 path (and shapes the fused kernel does not serve): S = scale q k^T, row softmax, O = P v as batched
         GEMMs over the [B,N,3,h,hd] layout; returns P (kept for the backward)"""
         S = self._empty(B * h, N, N, dtype=torch.float32)
         gemm(qkv, qkv, S, dtype=self.dtype, M=N, N=N, K=hd, lda=3 * D, ldb=3 * D, ldc=N, batch=B * h, batch_inner=h,
              sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(h * N * N, N * N), b_off=D, alpha=scale, c_f32=True)
         Pm = self._empty(B * h, N, N)
-        check(lib.htrvt_softmax_rows(ptr(S), ptr(Pm), B * h * N, N, self.dti, None, 0, st), "softmax_rows")
+        check(lib.htrvt_softmax_rows(ptr(S), ptr(Pm), B * h * N, N, self.dti, ptr(bias), h * N if bias is not None else 0, st),
+              "softmax_rows")
         del S
         gemm(Pm, qkv, O, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * h,
              batch_inner=h, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * D, hd), b_off=2 * D)
         return Pm
 
-    def _attention_bwd_unfused(self, qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st):
-        """float32 path (and shapes the fused kernel does not serve): batched GEMMs + row-softmax backward over the saved P"""
+    def _attention_bwd_unfused(self, qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st, dbias=None):
+        """float32 path (and shapes the fused kernel does not serve): batched GEMMs + row-softmax backward over the saved P.
+        dbias (window fork, float32 [h, N, N]): += d(score) summed over the batch (the scale then moves into the GEMMs)"""
         bstr = dict(batch=B * h, batch_inner=h)
         # dV = P^T dO
         gemm(Pm, dO, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
@@ -1083,12 +1172,15 @@ class Engine:
         gemm(dO, qkv, dP, dtype=self.dtype, M=N, N=N, K=hd, lda=D, ldb=3 * D, ldc=N, sA=(N * D, hd), sB=(N * 3 * D, hd),
              sC=(h * N * N, N * N), b_off=2 * D, c_f32=True, **bstr)
         dS = self._empty(B * h, N, N)
-        check(lib.htrvt_softmax_bwd_rows(ptr(Pm), ptr(dP), ptr(dS), B * h * N, N, scale, self.dti, st), "softmax_bwd_rows")
+        s_in, s_out = (scale, 1.0) if dbias is None else (1.0, scale)
+        check(lib.htrvt_softmax_bwd_rows(ptr(Pm), ptr(dP), ptr(dS), B * h * N, N, s_in, self.dti, st), "softmax_bwd_rows")
         del dP
+        if dbias is not None:
+            ops.colsum(dS, B, h * N * N, h * N * N, dbias, dti=self.dti)
         # dQ = dS K ; dK = dS^T Q
-        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, b_layout=MNMAJOR,
+        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, b_layout=MNMAJOR, alpha=s_out,
              sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=D, c_off=0, **bstr)
-        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, a_layout=MNMAJOR,
+        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, a_layout=MNMAJOR, alpha=s_out,
              b_layout=MNMAJOR, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=0, c_off=D, **bstr)
         del dS
 
@@ -1114,9 +1206,18 @@ class Engine:
 
         # sequence LN, head, final norm
         Cp = (C + 7) // 8 * 8           # class dim padded so that every 16-byte chunk is aligned
-        draw = torch.zeros(M, Cp, dtype=self.dtype, device=self.dev)
-        check(lib.htrvt_seq_whiten_bwd(ptr(dy), ptr(sv["y"]), ptr(sv["sstats"]), ptr(draw), B, N, C, Cp, self.dti, st),
-              "seq_whiten_bwd")
+        if s.whiten_logits:
+            draw = torch.zeros(M, Cp, dtype=self.dtype, device=self.dev)
+            check(lib.htrvt_seq_whiten_bwd(ptr(dy), ptr(sv["y"]), ptr(sv["sstats"]), ptr(draw), B, N, C, Cp, self.dti, st),
+                  "seq_whiten_bwd")
+        elif Cp == C and self.dtype == torch.float32:    # window fork: the gradient of the raw logits is dy itself
+            draw = dy.view(M, C)
+        elif Cp == C:
+            draw = self._empty(M, C)
+            check(lib.htrvt_cast_f32(ptr(dy), ptr(draw), M * C, self.dti, st), "cast_f32")
+        else:
+            draw = torch.zeros(M, Cp, dtype=self.dtype, device=self.dev)
+            draw[:, :C].copy_(dy.view(M, C))
         wh, wht = self._head_w(P["head.weight"])
         dxn = self.linear_dgrad(draw, wh, wht, plain=True)      # (split mode: the 80-class head stays on the float32 kernels)
         if Cp == C:
@@ -1147,7 +1248,9 @@ class Engine:
             self.linear_wgrad(dx1, e["O"], G[p + ".attn.proj.weight"], G[p + ".attn.proj.bias"])
             qkv, Pm = e["qkv"], e["P"]
             dqkv = self._empty(M, 3 * D)
-            if Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
+            if e.get("geo") is not None:
+                self._relpos_attention_bwd(P, G, e, dO, dqkv, B, N, D, h, hd, scale, st)
+            elif Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
                 delta = self._empty(B * h, N, dtype=torch.float32)
                 check(lib.htrvt_attn_bwd(ptr(qkv), None, ptr(e["O"]), ptr(dO), ptr(e["lse"]), ptr(delta), ptr(dqkv), None,
                                          B, N, h, hd, scale, self.dti, st), "attn_bwd")

@@ -173,6 +173,71 @@ def padded_len(N, dtype, head_dim):
     return _padded_len(N, dtype, head_dim)
 
 
+class _RelPosSelfAttention(torch.autograd.Function):
+    """qkv [B*N, 3*heads*hd] bfloat16 + table [(2P-1), heads] float32 -> out [B*N, heads*hd]: the table-driven fused kernels
+    (csrc/attn_relpos.hip), any N >= 32 with no padded copy; the table gradient is reduced without atomics"""
+
+    @staticmethod
+    def forward(ctx, qkv, table, B, N, heads, num_patches, window, shift):
+        D = qkv.shape[1] // 3
+        hd = D // heads
+        scale = hd ** -0.5
+        dti = dt(qkv.dtype)
+        if table.dtype != torch.float32:
+            raise TypeError(f"relative-position table: float32 expected (the parameter as stored), got {table.dtype}")
+        qkv, table = qkv.contiguous(), table.contiguous()
+        out = torch.empty(B * N, D, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(B * heads, N, dtype=torch.float32, device=qkv.device)
+        check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(table), ptr(out), ptr(lse), B, N, heads, hd, scale, num_patches, window,
+                                        shift, dti, stream()), "attn_relpos_fwd")
+        ctx.save_for_backward(qkv, table, out, lse)
+        ctx.dims = (B, N, heads, hd, scale, dti, num_patches, window, shift)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, N, h, hd, scale, dti, P, ws, shift = ctx.dims
+        qkv, table, out, lse = ctx.saved_tensors
+        dout = dout.contiguous().to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty(B * h, N, dtype=torch.float32, device=qkv.device)
+        dtable, work = None, None
+        if ctx.needs_input_grad[1]:
+            dtable = torch.zeros_like(table)
+            work = torch.empty(relpos_workspace_floats(B, N, h, P, ws, shift), dtype=torch.float32, device=qkv.device)
+        check(lib.htrvt_attn_relpos_bwd(ptr(qkv), ptr(table), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dtable),
+                                        ptr(work), B, N, h, hd, scale, P, ws, shift, dti, stream()), "attn_relpos_bwd")
+        return dqkv, dtable, None, None, None, None, None, None
+
+
+def relpos_supported(N, head_dim, dtype, num_patches, window_size=0, shift_size=0):
+    """True where the table-driven fused kernels serve the shape (bfloat16, hd in {64, 128}, 32 <= N <= P <= 2048)"""
+    return bool(lib.htrvt_attn_relpos_supported(N, head_dim, dt(dtype), num_patches, window_size, shift_size))
+
+
+def relpos_workspace_floats(B, N, heads, num_patches, window_size=0, shift_size=0):
+    n = lib.htrvt_attn_relpos_bwd_workspace_floats(B, N, heads, num_patches, window_size, shift_size)
+    if n < 0:
+        raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
+    return n
+
+
+def relpos_self_attention(qkv, table, B, N, heads, num_patches, window_size=0, shift_size=0):
+    """Attention.forward + Block._attend of the window fork on the qkv Linear's output: softmax(q k^T hd^-0.5 + table
+    bias) v with 1-D (shifted) windows, qkv [B*N, 3*heads*hd] (layout [B,N,3,heads,hd]), table [(2P-1), heads] float32.
+    bfloat16: the table-driven fused kernels (no dense bias, no padding); float32 (parity path): the dense bias of
+    relative_position_bias + batched GEMMs and row softmax (biased_self_attention).  Differentiable in qkv and table."""
+    if not (qkv.is_cuda and table.is_cuda):
+        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    hd = qkv.shape[1] // 3 // heads
+    if qkv.dtype == torch.bfloat16:
+        if not relpos_supported(N, hd, qkv.dtype, num_patches, window_size, shift_size):
+            raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
+        return _RelPosSelfAttention.apply(qkv, table, B, N, heads, num_patches, window_size, shift_size)
+    bias = relative_position_bias(table, N, num_patches, window_size, shift_size, ld=_padded_len(N, qkv.dtype, hd))
+    return biased_self_attention(qkv, bias, B, N, heads)
+
+
 class _CrossAttention(torch.autograd.Function):
     """SGMHead._cross_attend (sgm_head.py:118-127): out = softmax(Q K^T / sqrt(D)) K, Q [B,L,D], K = V [B,N,D]"""
 

@@ -284,6 +284,24 @@ int htrvt_relpos_bias_fwd(const float* table, float* bias, int N, int num_patche
 int htrvt_relpos_bias_bwd(const float* dbias, float* dtable, int N, int num_patches, int window, int shift, int heads, int ld,
                           void* stream);
 
+/* Fused bfloat16 self-attention with the relative-position bias TABLE of the window-attention fork (model_window/model/
+ * HTR_VT.py:11-62,113-154), forward and backward, any N >= 32 with no padded copy (csrc/attn_relpos.hip).  qkv / out /
+ * dout / dqkv / lse2 / delta as for htrvt_attn_*; table [(2P-1)][heads] float32 (P = num_patches, the parameter as stored).
+ * window 0: full attention, entry (key - query) + P - 1; window ws > 0: Np = ceil(N/ws) ws, pos = (t - shift) mod Np, a
+ * pair attends iff pos / ws agree and uses entry pos_key % ws - pos_query % ws + P - 1; every other pair is masked.
+ * _supported: 1 if (N, hd, dtype, geometry) is served -- bfloat16, hd in {64, 128}, 32 <= N <= P <= 2048, 0 <= shift < ws
+ * (shift 0 without a window; a shifted window needs N > ws) -- else 0 with the reason in htrvt_last_error().
+ * _bwd: dtable (may be NULL: no table gradient) += d(loss)/d(table), float32, no atomics: per-workgroup partial rows in
+ * `workspace` (htrvt_attn_relpos_bwd_workspace_floats() floats, -1 on bad geometry) summed in a fixed order -- bitwise
+ * reproducible. */
+int htrvt_attn_relpos_supported(int N, int hd, int dtype, int num_patches, int window, int shift);
+int64_t htrvt_attn_relpos_bwd_workspace_floats(int B, int N, int heads, int num_patches, int window, int shift);
+int htrvt_attn_relpos_fwd(const void* qkv, const float* table, void* out, float* lse2, int B, int N, int heads, int hd,
+                          float scale, int num_patches, int window, int shift, int dtype, void* stream);
+int htrvt_attn_relpos_bwd(const void* qkv, const float* table, const void* out, const void* dout, const float* lse2,
+                          float* delta, void* dqkv, float* dtable, float* workspace, int B, int N, int heads, int hd,
+                          float scale, int num_patches, int window, int shift, int dtype, void* stream);
+
 /* ---- weight layout helpers ----------------------------------------------------- */
 /* w [Co][Ci][taps] float32 -> fwd [Co][taps][cpad_in], dgrad [Ci][taps][cpad_out] (may be NULL); pads untouched */
 int htrvt_pack_conv_weight(const float* w, void* fwd, void* dgrad, int Co, int Ci, int taps, int cpad_in,

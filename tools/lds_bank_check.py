@@ -20,7 +20,7 @@ HALVES = [list(range(32)), list(range(32, 64))]
 
 
 def off(hd, row, ch):
-    """byte offset of 16-byte chunk `ch` of row `row` of a [rows][hd] bf16 tile (csrc/attention.hip: lds_off<HD>)"""
+    """byte offset of 16-byte chunk `ch` of row `row` of a [rows][hd] bf16 tile (csrc/attention_common.h: lds_off<HD>)"""
     if hd == 128:      # 256-B rows
         return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)))
     if hd == 64:       # 128-B rows, two per bank row
