@@ -127,6 +127,14 @@ PROTOTYPES = {
     "htrvt_line_prepare": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "htrvt_ctc_workspace_floats": (C.c_size_t, [i32, i32, i32]),
     "htrvt_ctc_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
+    "htrvt_sgm_context": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "htrvt_sgm_query_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "htrvt_sgm_query_bwd_workspace_floats": (i64, [i32, i32, i32, i32]),
+    "htrvt_sgm_query_bwd": (i32, [vp] * 7 + [i32, i32, i32, i32, i32, i32, vp]),
+    "htrvt_sgm_dropout": (i32, [vp, vp, i64, vp, f32, i32, vp]),
+    "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "htrvt_sgm_xent_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "htrvt_sgm_convert": (i32, [vp, i32, vp, i32, i64, i32, vp]),
 }
 
 

@@ -887,11 +887,15 @@ class Engine:
         return dx
 
     # ------------------------------------------------------------------ forward
-    def forward(self, P, img, keep_mask=None, train=False, save=False):
+    def forward(self, P, img, keep_mask=None, train=False, save=False, want_features=False):
         """P: dict name -> float32 device tensor (parameters and BN buffers, reference state_dict names).
         img: [B,1,H,W] float32.  keep_mask: None or float32 [N] (1 keep / 0 mask-token).
-        Returns float32 logits [B,N,nb_cls] (after the final param-free LayerNorm)."""
+        Returns float32 logits [B,N,nb_cls] (after the final param-free LayerNorm); want_features: (logits, feats) with
+        feats the final norm's output as a fresh float32 [B,N,D] tensor (the SGM forks' feature tap)."""
         s = self.s
+        if want_features and self.split:
+            raise NotImplementedError("split_bf16 has no feature output: use compute_dtype=torch.float32 (parity) or "
+                                      "torch.bfloat16")
         if train and s.dropout:
             raise NotImplementedError("train-mode forward of a model with dropout / drop-path: not implemented (build the "
                                       "window model with create_model(..., dropout=False) to train without them)")
@@ -1102,6 +1106,10 @@ class Engine:
         if save:
             sv.update(enc=enc_saved, x_last=xt, xn=xn, mn=mn, rn=rn, y=y, sstats=sstats, B=B, N=N, train=train)
             self.saved = sv
+        if want_features:       # a copy: xn is kept for the head's weight gradient and must not be written by the caller
+            feats = torch.empty(B, N, D, dtype=torch.float32, device=self.dev)
+            check(lib.htrvt_sgm_convert(ptr(xn), self.dti, ptr(feats), 0, M * D, 0, st), "sgm_convert")
+            return y, feats
         return y
 
     def _relpos_attention_fwd(self, P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st):
@@ -1185,9 +1193,11 @@ class Engine:
         del dS
 
     # ------------------------------------------------------------------ backward
-    def backward(self, P, G, dy, after_encoder=None, after_layer3=None):
-        """dy: float32 [B,N,C] = dLoss/dlogits.  Accumulates dLoss/dparam into G (dict name -> float32 tensor,
-        same shapes as P; the caller zeroes it).  Uses the activations saved by forward(save=True)."""
+    def backward(self, P, G, dy, after_encoder=None, after_layer3=None, dfeats=None):
+        """dy: float32 [B,N,C] = dLoss/dlogits (None: only the features carry a loss).  dfeats: None or float32 [B,N,D] =
+        dLoss/dfeats of forward(want_features=True), added to the final norm's output gradient.  Accumulates dLoss/dparam
+        into G (dict name -> float32 tensor, same shapes as P; the caller zeroes it).  Uses the activations saved by
+        forward(save=True)."""
         sv = self.saved
         assert sv is not None, "backward() needs forward(..., save=True)"
         s = self.s
@@ -1195,14 +1205,26 @@ class Engine:
         B, N, D = sv["B"], sv["N"], s.D
         M = B * N
         C = s.nb_cls
-        h, hd = s.heads, s.hd
-        scale = hd ** -0.5
-        dy = dy.contiguous()
+        assert dy is not None or dfeats is not None, "backward() needs dy and / or dfeats"
+        if dfeats is not None:
+            dfeats = dfeats.contiguous()
+            assert dfeats.dtype == torch.float32 and dfeats.shape == (B, N, D) and not self.split
         self._zarena_begin()
         self._pending_unpack = []
         self._bn_train = bool(sv["train"])
-        assert dy.dtype == torch.float32 and dy.shape == (B, N, C)
         self._side_active = self.overlap_wgrad and not self.single_stream
+        if dy is None:          # features-only loss: the head and the logits' LayerNorm get no gradient
+            dxn = self._empty(M, D)
+            check(lib.htrvt_sgm_convert(ptr(dfeats), 0, ptr(dxn), self.dti, M * D, 0, st), "sgm_convert")
+        else:
+            dxn = self._head_backward(P, G, sv, dy.contiguous(), B, N, M, C, D, st)
+            if dfeats is not None:
+                check(lib.htrvt_sgm_convert(ptr(dfeats), 0, ptr(dxn), self.dti, M * D, 1, st), "sgm_convert")
+        self._encoder_backward(P, G, sv, dxn, after_encoder, after_layer3)
+
+    def _head_backward(self, P, G, sv, dy, B, N, M, C, D, st):
+        s = self.s
+        assert dy.dtype == torch.float32 and dy.shape == (B, N, C)
 
         # sequence LN, head, final norm
         Cp = (C + 7) // 8 * 8           # class dim padded so that every 16-byte chunk is aligned
@@ -1228,6 +1250,15 @@ class Engine:
             self._join_side()
             check(lib.htrvt_rowsum_f32(ptr(dwp), 1, C * D, ptr(G["head.weight"]), st), "rowsum")
             check(lib.htrvt_rowsum_f32(ptr(dbp), 1, C, ptr(G["head.bias"]), st), "rowsum")
+        return dxn
+
+    def _encoder_backward(self, P, G, sv, dxn, after_encoder, after_layer3):
+        s = self.s
+        st = stream()
+        B, N, D = sv["B"], sv["N"], s.D
+        M = B * N
+        h, hd = s.heads, s.hd
+        scale = hd ** -0.5
         dx = self.ln_bwd(dxn, sv["x_last"], sv["mn"], sv["rn"], P["norm.weight"], None, G["norm.weight"], G["norm.bias"])
 
         for e in reversed(sv["enc"]):

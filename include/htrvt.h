@@ -421,6 +421,36 @@ int htrvt_line_max_scale(void);
 int htrvt_line_prepare(const uint8_t* src, const HtrvtLineImage* table, uint8_t* tmp, uint8_t* dst, int B, int H, int W,
                        int max_src_h, void* stream);
 
+/* ---- the SGM forks' semantic-guidance head (csrc/sgm.hip; sgm_head.py of every model_sgm_ fork) ---------------------------
+ * Row r of the head's query batch is (b, dir, l) of [B][2][L]: dir 0 = the left windows, 1 = the right windows.
+ * htrvt_sgm_context: make_context_batch (:29-73).  table int32 = [B] offsets into the ids, [B] lengths, the packed ids;
+ *   left / right int64 [B][Lmax][S], tgt int64 [B][Lmax], mask float32 [B][Lmax]; positions past a line hold pad_id / 0.
+ * htrvt_sgm_query_fwd: out[r][:] (dtype) = mean over S of emb[id] + dir token (_context_to_query up to txt_proj); ids are
+ *   clamped into [0, V).  _bwd: demb [V][d_txt], ddir_* [d_txt] overwritten, per-chunk LDS sums then an ordered sum over
+ *   the chunks (workspace: htrvt_sgm_query_bwd_workspace_floats floats); no atomics.  V <= 254.
+ * htrvt_sgm_dropout: y = x * keep / (1 - p), keep drawn from (seed[0], element index) by a counter-based hash; seed is a
+ *   device int64.  The backward is the same call on the gradient.  n a multiple of 4 (float32) / 8 (bfloat16).
+ * htrvt_sgm_xent_fwd: logits float32 [2 B L][ldv]: row log-softmax over the first V columns, NLL at tgt (clamped) times
+ *   mask; logits_l / logits_r (may be NULL) float32 [B][L][V] copies; lse, rowloss [2 B L] scratch kept for the backward;
+ *   den[0] = 2 max(sum mask, 1), loss[0] = sum / den[0], both by a fixed-shape ordered reduction.
+ * htrvt_sgm_xent_bwd: dlogits [2 B L][ldv] (dtype) = (softmax - onehot) * mask * g[0] / den[0] (+ dlogits_l / _r, may be
+ *   NULL; g may be NULL = 0), zero in the columns V .. ldv-1.
+ * htrvt_sgm_convert: dst = src (accumulate: dst += src), element types src_dtype / dst_dtype. */
+int htrvt_sgm_context(const int32_t* table, int B, int Lmax, int S, int pad_id, int bos_left_id, int bos_right_id, int eos_id,
+                      int64_t* left, int64_t* right, int64_t* tgt, float* mask, void* stream);
+int htrvt_sgm_query_fwd(const int64_t* left, const int64_t* right, const float* emb, const float* dir_left,
+                        const float* dir_right, void* out, int B, int L, int S, int V, int d_txt, int dtype, void* stream);
+int64_t htrvt_sgm_query_bwd_workspace_floats(int B, int L, int V, int d_txt);
+int htrvt_sgm_query_bwd(const int64_t* left, const int64_t* right, const void* dq, float* workspace, float* demb,
+                        float* ddir_left, float* ddir_right, int B, int L, int S, int V, int d_txt, int dtype, void* stream);
+int htrvt_sgm_dropout(const void* x, void* y, int64_t n, const int64_t* seed, float p, int dtype, void* stream);
+int htrvt_sgm_xent_fwd(const float* logits, int ldv, int V, int B, int L, const int64_t* tgt, const float* mask,
+                       float* logits_l, float* logits_r, float* lse, float* rowloss, float* loss, float* den, void* stream);
+int htrvt_sgm_xent_bwd(const float* logits, int ldv, int V, int B, int L, const int64_t* tgt, const float* mask,
+                       const float* lse, const float* den, const float* g, const float* dlogits_l, const float* dlogits_r,
+                       void* dlogits, int dtype, void* stream);
+int htrvt_sgm_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
