@@ -47,7 +47,6 @@ struct RelParams {
   float scale;
   int P, win, shift, Np, R;
   int ncode;           // tokens with a code in LDS: N rounded up to 128
-  int skip;            // skip key / query tiles nothing in the workgroup can see (windowed attention only)
 };
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -84,7 +83,7 @@ __device__ __forceinline__ bool win_has(const WinSet& s, int w, int nw) {
 
 // can some token of [a0, a1] attend to some token of [b0, b1]?  (workgroup-uniform; full attention: always)
 __device__ __forceinline__ bool tiles_meet(const RelParams& p, int a0, int a1, int b0, int b1) {
-  if (p.win <= 0 || !p.skip) return true;
+  if (p.win <= 0) return true;
   const int nw = p.Np / p.win;
   const WinSet A = win_set(p, a0, a1), Bs = win_set(p, b0, b1);
   return max(A.lo, Bs.lo) <= min(A.hi, Bs.hi) || (A.last && win_has(Bs, nw - 1, nw)) || (Bs.last && win_has(A, nw - 1, nw));
@@ -590,8 +589,6 @@ RelParams make_params(const void* qkv, const float* table, int B, int N, int hea
   p.Np = win > 0 ? ceil_div(N, win) * win : N;
   p.R = win > 0 ? win : P;
   p.ncode = ceil_div(N, 128) * 128;
-  static const bool noskip = getenv("HTRVT_NO_RELPOS_SKIP") != nullptr && getenv("HTRVT_NO_RELPOS_SKIP")[0] == '1';   // A/B runs on one box
-  p.skip = noskip ? 0 : 1;
   return p;
 }
 

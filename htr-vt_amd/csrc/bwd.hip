@@ -320,7 +320,7 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ partial, int ro
 // pass B: dx = cA*g + cB*x + cC ; optionally also writes g (the ReLU-masked incoming gradient)
 // The 3 C coefficients sit in LDS (per element loads from global were 24 of the 27 loads of a vector) and the channel
 // index of a thread's vector advances by a constant per grid stride (no 64-bit modulo per vector).
-// STREAM: the inputs by non-temporal loads (ld_stream16) -- activations of >= bn_stream_bytes() that no cache will hold until their
+// STREAM: the inputs by non-temporal loads (ld_stream16) -- activations of >= BN_STREAM_BYTES that no cache will hold until their
 // next reader; smaller ones (layer 3: 50 MB) are served from the memory-side cache and lose with them (A/B in profiles/r05_experiments.md (m))
 template <typename T, bool STREAM>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_kernel(const T* __restrict__ dy, const T* __restrict__ yact,
@@ -903,7 +903,7 @@ extern "C" int htrvt_bn_bwd_apply(const void* dy, const void* yact, const void* 
   HTRVT_REQUIRE(C % ch == 0, "htrvt_bn_bwd_apply: C=%d unsupported", C);
   const long long nvec = npix * (C / ch);
   dim3 grid(grid_for(nvec));
-  if (nvec * 16 >= bn_stream_bytes()) {
+  if (nvec * 16 >= BN_STREAM_BYTES) {
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), grid, dim3(NT), (size_t)3 * C * sizeof(float), (hipStream_t)stream, (const T*)dy,
                                          (const T*)yact, (const T*)x, coef, (T*)dx, (T*)gout, nvec, C));
   } else {
@@ -920,7 +920,7 @@ extern "C" int htrvt_bn_bwd_apply2(const void* g, const void* x1, const float* c
   HTRVT_REQUIRE(g && x1 && x2 && coef1 && coef2 && dx1 && dx2, "htrvt_bn_bwd_apply2: null buffer");
   const long long nvec = npix * (C / ch);
   dim3 grid(grid_for(nvec));
-  if (nvec * 16 >= bn_stream_bytes()) {
+  if (nvec * 16 >= BN_STREAM_BYTES) {
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply2_kernel<T, true>), grid, dim3(NT), (size_t)6 * C * sizeof(float), (hipStream_t)stream, (const T*)g,
                                          (const T*)x1, coef1, (T*)dx1, (const T*)x2, coef2, (T*)dx2, nvec, C));
   } else {

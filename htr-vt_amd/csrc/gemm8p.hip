@@ -94,8 +94,6 @@ bool gemm8p_serves(const HtrvtGemmDesc* d) {
 // schedule with transposed fragment reads (gemm8pt_impl.h).  tile 0 (auto) and 16; 3 / 4 / 6 keep naming the older kernels.
 bool gemm8pt_serves(const HtrvtGemmDesc* d) {
   if (d->tile != 0 && d->tile != 16) return false;
-  static const bool off = getenv("HTRVT_NO_MNMAJOR_8PHASE") != nullptr && getenv("HTRVT_NO_MNMAJOR_8PHASE")[0] == '1';   // A/B runs on one box
-  if (off && d->tile == 0) return false;
   if (d->dtype != HTRVT_BF16 || d->gather != HTRVT_GATHER_NONE || d->a_layout != HTRVT_MNMAJOR || d->b_layout != HTRVT_MNMAJOR) return false;
   if (!d->c_f32 || d->batch > 1 || d->M < 256 || d->N < 256 || d->K < 256) return false;
   // auto: outputs of at least 16 tiles of 256 x 256.  The proj weight gradient (768 x 768: 9 tiles) needs a 20-28-way K split to
@@ -147,8 +145,7 @@ int gemm8p_try_launch(const HtrvtGemmDesc* d, KParams& p, int zdim, hipStream_t 
   if (d->gather == HTRVT_GATHER_NONE) {
     // Persistent walk (gemm8pp_impl.h): one workgroup per CU, the DMA stream and the k loop run through the tile boundaries,
     // the epilogue of a tile is folded into the first k-tile of the next.  tile 0 (auto) and 13; 9-11 keep naming the
-    // one-tile-per-workgroup kernels (A/B runs, tests).  HTRVT_NO_PERSISTENT_GEMM=1 switches the auto route off.
-    static const bool off = getenv("HTRVT_NO_PERSISTENT_GEMM") != nullptr && getenv("HTRVT_NO_PERSISTENT_GEMM")[0] == '1';
+    // one-tile-per-workgroup kernels (tests).
     const long long ntiles = (long long)p.tiles_m * p.tiles_n;
     // auto: the plain / bias epilogue only.  With the GELU epilogue the folded flush is VALU-bound -- one wave per SIMD
     // evaluates erf while its partner's 16 MFMAs are long done -- and measured 2-3 % SLOWER than the unfolded epilogue, in
@@ -156,9 +153,8 @@ int gemm8p_try_launch(const HtrvtGemmDesc* d, KParams& p, int zdim, hipStream_t 
     // round 5: bias + residual too (192-column tiles: proj / fc2 forward), the residual through registers (gemm8pp_impl.h)
     // (* GELU'(saved pre-activation) through the same register loads was built and measured 7 % SLOWER than the one-tile kernel:
     // its flush is VALU-bound on one wave per SIMD, profiles/r05_experiments.md (g))
-    static const bool res_off = getenv("HTRVT_NO_PERSISTENT_RES") != nullptr && getenv("HTRVT_NO_PERSISTENT_RES")[0] == '1';
-    const bool res_ok = epi == E_RES && bn == 192 && !res_off && d->K >= 256 && (reinterpret_cast<unsigned long long>(d->residual) & 3) == 0;
-    const bool want = (d->tile >= 13 && d->tile <= 15) || (d->tile == 0 && !off && (epi == 0 || res_ok));
+    const bool res_ok = epi == E_RES && bn == 192 && d->K >= 256 && (reinterpret_cast<unsigned long long>(d->residual) & 3) == 0;
+    const bool want = (d->tile >= 13 && d->tile <= 15) || (d->tile == 0 && (epi == 0 || res_ok));
     if (want && (epi == 0 || epi == E_GELU || res_ok) && zdim == 1 && d->batch <= 1 && d->K % 128 == 0 && d->K >= 256 &&
         (reinterpret_cast<unsigned long long>(d->bias) & 15) == 0 && (d->preact == nullptr || (reinterpret_cast<unsigned long long>(d->preact) & 15) == 0)) {
       static int ncu = 0;

@@ -86,8 +86,7 @@ int gemm_dma_try_launch(const HtrvtGemmDesc* d, KParams& p, int zdim, hipStream_
   if (d->dtype != HTRVT_BF16 || d->M <= 128 || d->tile == 1 || !extents_ok(d)) return 0;
   if (d->gather == HTRVT_GATHER_CONV_DGRAD && d->cls_h == -2) return gemm_halo_s2_try_launch(d, p, st, false);   // all parity classes, one launch
   if (d->gather == HTRVT_GATHER_CONV_FWD && d->kh == 1 && d->kw == 1) {   // strided 1x1 downsample convolutions: HBM-rate streaming kernel (conv1x1.hip)
-    static const bool off = getenv("HTRVT_NO_CONV1X1") != nullptr && getenv("HTRVT_NO_CONV1X1")[0] == '1';   // A/B runs on one box
-    const int r = off ? 0 : conv1x1_try_launch(d, p, st);
+    const int r = conv1x1_try_launch(d, p, st);
     if (r != 0) return r;
   }
   if (d->relu_src != nullptr || d->bnb_partial[0] != nullptr) {

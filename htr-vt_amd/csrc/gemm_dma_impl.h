@@ -23,17 +23,6 @@ using namespace htrvt;
 
 namespace {
 
-#ifdef HTRVT_EXP_STAMP
-__device__ unsigned long long htrvt_dbg[16 * 8192];   // one per translation unit (experiment builds only)
-#define HTRVT_STAMP(slot)                                                                         \
-  do {                                                                                            \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) htrvt_dbg[blockIdx.x * 16 + (slot)] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define HTRVT_STAMP(slot) do { } while (0)
-#endif
-
-
 constexpr int BK = 64;
 constexpr unsigned OOB = 0x80000000u;
 
@@ -70,11 +59,6 @@ __device__ __forceinline__ void xcd_range_map(int b, int total, int ntiles, int&
   const int L = x * q + (x < r ? x : r) + s;
   z = L / ntiles;
   id = L - z * ntiles;
-}
-
-inline bool hwgrad_xcd_ranges() {      // HTRVT_NO_XCD_RANGES=1: the z-grid of rounds 3-4 for split factors that are not multiples of 8 (A/B runs)
-  static const bool off = getenv("HTRVT_NO_XCD_RANGES") != nullptr && getenv("HTRVT_NO_XCD_RANGES")[0] == '1';
-  return !off;
 }
 
 template <int ROWS, int NWAVES = 8, int KB = 64>   // KB = k-tile depth in elements (64, or 32 for the deep pipeline)
@@ -461,9 +445,7 @@ __device__ __forceinline__ void epilogue_staged(f32x16_t (&acc)[2][TN], const P&
     }
   }
   }
-  HTRVT_STAMP(4);
   __syncthreads();
-  HTRVT_STAMP(5);
   // ---- phase 2: LDS -> (act / residual) -> global, 16 B per lane, 4 lanes = 64 contiguous bytes of one row ----
   // Items are processed U at a time: all global loads of the U items (residual, ReLU source, BN inputs, saved
   // pre-activation) are issued first from clamped, always-valid offsets, then the transposed LDS reads, then the
@@ -797,7 +779,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
   constexpr int STAGE = A_BYTES + B_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  HTRVT_STAMP(0);
   const int ntiles = p.tiles_m * p.tiles_n;
   int id = block_x;
   int z = blockIdx.z;
@@ -883,7 +864,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
       if (BST == 3) lb.template issue<KMAP>(p, lds0 + B_BASE + B_BYTES, kbeg + BK, kend, lw);
     }
   }
-  HTRVT_STAMP(1);
   if (NSTAGE == 3 && nkt > 1)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");
   else if (NSTAGE == 5 && nkt > 1)
@@ -891,7 +871,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
   else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  HTRVT_STAMP(2);
 
   int a_cur = 0, a_nxt = AST - 1;   // A buffer being multiplied / A buffer the DMA issued in this iteration fills
   int b_cur = 0, b_nxt = BST - 1;
@@ -902,11 +881,7 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
   // read the fragments of a k-tile's last two k-steps into registers before the barrier and multiply them after it,
   // while waves 0-3 issue their DMA; then they issue theirs while waves 0-3 multiply.  (MI355X_MICROARCH.md, Two waves per
   // SIMD, item 9: split by wave number >= 4.)
-#ifdef HTRVT_EXP_NOSTAGGER
-  constexpr bool STAGGER = false;
-#else
   constexpr bool STAGGER = SPEC == 0 && NSTAGE == 2 && AL == HTRVT_MNMAJOR;
-#endif
   const bool late = STAGGER && wave >= NWC / 2;
   auto advance = [&]() {
     a_cur = (a_cur + 1 == AST) ? 0 : a_cur + 1;
@@ -920,7 +895,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
     for (int kt = 0; kt < nkt; ++kt) {
       const char* sa = smem + a_cur * A_BYTES;
       const char* sb = smem + B_BASE + b_cur * B_BYTES;
-#ifndef HTRVT_EXP_NOMMA
       if (kt > 0) {          // k-steps 2, 3 of k-tile kt-1, from registers: runs beside the early waves' DMA issue
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -932,14 +906,10 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
           for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha1[i], hb1[j], acc[i][j], 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifndef HTRVT_EXP_NODMA
       if (kt + 1 < nkt) {
         lb.template issue<KMAP>(p, lds0 + B_BASE + b_nxt * B_BYTES, kbeg + (kt + 1) * BK, kend, lw);
         la.issue(p, lds0 + a_nxt * A_BYTES, kbeg + (kt + 1) * BK, kend, lw);
       }
-#endif
-#ifndef HTRVT_EXP_NOMMA
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         bf16x8_t fa[TM], fb[TN];
@@ -964,12 +934,10 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
         hb1[j] = frag_read<BN, BL>(sb, wn * TN + j, 3, lane);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the held fragments are in registers before this stage is refilled
-#endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       advance();
     }
-#ifndef HTRVT_EXP_NOMMA
     if (nkt > 0) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -980,7 +948,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha1[i], hb1[j], acc[i][j], 0, 0, 0);
     }
-#endif
   } else if (SPEC && consumer) {
     // loader-wave kernels (round 5): the MFMA waves run their OWN copy of the loop -- fragment reads and MFMAs between barriers,
     // nothing else -- instead of walking the loaders' branches (gemm_halo_impl.h: -5 ... -9 % per launch on the halo kernels)
@@ -1008,17 +975,11 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
     const char* sa = smem + a_cur * A_BYTES;
     const char* sb = smem + B_BASE + b_cur * B_BYTES;
     const int kt_a = kt + AST - 1, kt_b = kt + BST - 1;
-#ifndef HTRVT_EXP_NODMA
     if (loader) {   // B first: its (shorter) run-ahead makes it the latency-critical one
       if (kt_b < nkt) lb.template issue<KMAP>(p, lds0 + B_BASE + b_nxt * B_BYTES, kbeg + kt_b * BK, kend, lw);
       if (kt_a < nkt) la.issue(p, lds0 + a_nxt * A_BYTES, kbeg + kt_a * BK, kend, lw);
     }
-#endif
-#ifdef HTRVT_EXP_NOMMA
-    if (false) {
-#else
     if (consumer) {
-#endif
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         bf16x8_t fa[TM], fb[TN];
@@ -1045,7 +1006,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
   }
   }
 
-  HTRVT_STAMP(3);
   // uniform choice: bf16 C with 16-byte-aligned rows -> staged, vectorised epilogue; float32 C -> direct
   // (256-column tiles serve the float32 split-K weight gradients; their bf16 output, explicit tile selector only,
   //  takes the direct epilogue: the staged one would not leave the loaders' descriptors their SGPRs)
@@ -1055,16 +1015,6 @@ __device__ __forceinline__ void gemm_dma_body(const P& p, const int block_x) {
   } else
     gemm_epilogue<T, TM, TN, BM / 64, BN, NTH, false>(acc, p, p.C, coff, m0 + wm * TM * 32, n0 + wn * TN * 32, wm, n0, tile_m, lane,
                                                smem, consumer);
-  HTRVT_STAMP(6);
-#ifdef HTRVT_EXP_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  HTRVT_STAMP(7);
-  if (threadIdx.x == 0 && blockIdx.x < 8192) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    htrvt_dbg[blockIdx.x * 16 + 8] = hw;
-  }
-#endif
 }
 
 template <int BM, int BN, int AL, int BL, int GATHER, int SPEC, int NSTAGE = 2>
@@ -1093,7 +1043,7 @@ int launch(const KParams& p, int zdim, hipStream_t st) {
     attr_done = true;
   }
   dim3 grid(p.tiles_m * p.tiles_n, 1, zdim);
-  if (p.split_k > 1 && ((p.split_k & 7) == 0 || hwgrad_xcd_ranges())) grid = dim3(p.split_k * p.tiles_m * p.tiles_n, 1, 1);   // XCD-grouped K ranges
+  if (p.split_k > 1) grid = dim3(p.split_k * p.tiles_m * p.tiles_n, 1, 1);   // XCD-grouped K ranges
   hipLaunchKernelGGL(kern, grid, dim3(NTH), smem, st, p);
   set_last_kernel("gemm_dma_kernel<%d, %d, %d, %d, %d, %d, %d>", BM, BN, AL, BL, GATHER, SPEC, NSTAGE);
   const int rc = check_launch("gemm_dma_kernel");

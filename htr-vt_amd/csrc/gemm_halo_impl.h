@@ -11,8 +11,8 @@
 // instead of 3 x 56 KB.  The freed LDS pays for a third B stage: B runs two k-tiles ahead, the halo tile a whole group
 // ahead, and every wait is a counted vmcnt that leaves the newest k-tile's pieces in flight.
 //
-// Structure otherwise as gemm_dma_kernel<256, BN, .., SPEC = 1>: 8 MFMA waves (4 x 2, v_mfma_f32_32x32x16_bf16) + 4
-// loader waves, one barrier per k-tile, the LDS-staged bf16 epilogue (BatchNorm column sums; backward-of-ReLU mask and
+// Structure otherwise as gemm_dma_kernel<256, BN, .., SPEC = 1>: 8 MFMA waves (4 x 2, v_mfma_f32_16x16x32_bf16: halo_mma16)
+// + 4 loader waves, one barrier per k-tile, the LDS-staged bf16 epilogue (BatchNorm column sums; backward-of-ReLU mask and
 // BatchNorm-backward sums on dgrad) shared with that kernel.
 #pragma once
 #include "gemm_dma_impl.h"
@@ -39,7 +39,7 @@ struct HaloGeo {
 // 4 s + (l >> 4).  Measured against the v_mfma_f32_32x32x16_bf16 form of the same loop (same bytes from LDS, same
 // cycles per FLOP): +2.4 ... +6 % on every stride-1 3x3 convolution of the stem, forward and dgrad
 // (profiles/r05_experiments.md) -- the chip holds a higher clock on this shape (MI355X_MICROARCH.md, DVFS give-back,
-// item 7).  -DHTRVT_HALO_MFMA32 builds the former form (A/B runs).
+// item 7).
 typedef float f32x4h_t __attribute__((ext_vector_type(4)));
 template <int BN, int TM, int TN>
 __device__ __forceinline__ void halo_mma16(f32x4h_t (&a4)[2 * TM][2 * TN], const char* sa, const char* sb, int shift, int wm, int wn,
@@ -152,166 +152,6 @@ __device__ __forceinline__ void halo_epilogue_f32(const f32x4h_t (&a4)[2 * TM][2
       }
     }
   }
-}
-
-// DGRAD = false: A rows = output pixels, source = x [B,H,W,Ci];  true: A rows = input pixels, source = dy [B,H,W,Co]
-template <int BN, bool DGRAD, class P>
-__device__ __forceinline__ void gemm_halo_body_oneloop(const P& p, const int block_x) {
-  using H = HaloGeo<BN>;
-  constexpr int BM = 256, NWC = 8, NW_TOTAL = 12, TM = 2, TN = BN / 64;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int ntiles = p.tiles_m * p.tiles_n;
-  int id = block_x;
-  if ((ntiles & 7) == 0) id = (id & 7) * (ntiles >> 3) + (id >> 3);
-  const int tile_m = id / p.tiles_n, tile_n = id - tile_m * p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int Hh = DGRAD ? p.Ho : p.Hi, Ww = DGRAD ? p.Wo : p.Wi, Cs = DGRAD ? p.Co : p.Ci;   // gathered tensor [B,Hh,Ww,Cs]
-  const int rowi = m0 / Ww, w0 = m0 - rowi * Ww;      // row (b * Hm + h) of the M index space and first column of this tile
-  // forward with a row stride (sh = 2, W stride 1: the first conv of layer 1): M rows are OUTPUT rows, Hm = Ho of them per
-  // image, and kernel row gdy of output row h reads input row h * sh + gdy - 1; dgrad is served at stride 1 only
-  const int Hm = DGRAD ? Hh : p.Ho;
-  const int bimg = rowi / Hm, hrow = rowi - bimg * Hm;
-  const int NC = p.Cpad / BK;                           // 64-channel chunks per tap
-  const int NG = 3 * NC;                                // groups = (kernel row, chunk); k-tiles = 3 * NG
-
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool consumer = wave < NWC;
-  const int lw = (wave - NWC) & 3;
-  const int wm = (wave >> 1) & 3, wn = wave & 1;
-  if (!consumer) __builtin_amdgcn_s_setprio(3);
-
-  // ---- loader state ----
-  DmaLoader<BN, HTRVT_KMAJOR, 0, 4> lb;
-  lb.init(p, p.B, p.ldb, n0, p.N, lw, lane);
-  const unsigned long long ba = (unsigned long long)p.A;
-  const i32x4_t rsrcA = i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), (int)OOB, 0x00020000};
-  // this lane's first halo row (piece lw) and source chunk; piece lw + 4 i is 32 i rows further down, same swizzle
-  const int rho0 = lw * 8 + (lane >> 3);
-  const int cgA = (lane & 7) ^ Geo<BM>::swz(rho0);
-  const unsigned lane_off = (unsigned)((w0 - 1 + rho0) * Cs + cgA * 8) * 2u;   // may wrap for w0 - 1 + rho0 < 0: masked below
-  const unsigned lds0 = lds_addr_of(smem);
-
-  // A halo half `half` (pieces 20 half .. 20 half + 19) of group (gdy, gcc) into A stage `ast`; gvalid false: zero fill
-  auto issueA = [&](int half, int ast, int gdy, int gcc, bool gvalid) {
-    const int hh = DGRAD ? hrow + 1 - gdy : hrow * p.sh + gdy - 1;
-    const bool rowok = gvalid && (unsigned)hh < (unsigned)Hh;
-    const unsigned gbase = (unsigned)(((bimg * Hh + hh) * Ww) * Cs + gcc * BK) * 2u;
-    const bool chok = gcc * BK + cgA * 8 < Cs;
-#pragma unroll
-    for (int i = 0; i < H::NP_AH; ++i) {
-      const int ii = half * H::NP_AH + i;
-      const int rho = rho0 + 32 * ii;
-      const int w = w0 - 1 + rho;
-      const bool v = rowok && chok && rho < 258 && (unsigned)w < (unsigned)Ww;
-      const unsigned voff = v ? gbase + lane_off + (unsigned)(32 * ii * Cs) * 2u : OOB;
-      dma16(rsrcA, __builtin_amdgcn_readfirstlane(lds0 + ast * H::A_STAGE + (lw + 4 * ii) * 1024), voff);
-    }
-  };
-  // B tile of k-tile (gdy, gcc, dx) into B stage `bst`
-  auto issueB = [&](int bst, int gdy, int gcc, int dx, bool gvalid) {
-    const int k0 = gvalid ? (gdy * 3 + dx) * p.Cpad + gcc * BK : p.K;      // >= K: zero fill
-    lb.template issue<true>(p, lds0 + H::B_BASE + bst * H::B_STAGE, k0, p.K, lw);
-  };
-
-  f32x16_t acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // ---- prologue: halo tile of group 0, B of k-tiles 0 and 1 ----
-  if (!consumer) {
-    issueA(0, 0, 0, 0, true);
-    issueA(1, 0, 0, 0, true);
-    issueB(0, 0, 0, 0, true);
-    issueB(1, 0, 0, 1, true);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B) : "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-
-  // consumer fragment addressing: A row = wm*64 + i*32 + (lane & 31) + shift
-  const int arow = wm * 64 + (lane & 31), ah = lane >> 5;
-#ifndef HTRVT_HALO_MFMA32
-  f32x4h_t a4[2 * TM][2 * TN];
-#pragma unroll
-  for (int i = 0; i < 2 * TM; ++i)
-#pragma unroll
-    for (int j = 0; j < 2 * TN; ++j) a4[i][j] = f32x4h_t{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](const char* sa, const char* sb, int shift) { halo_mma16<BN, TM, TN>(a4, sa, sb, shift, wm, wn, lane); };
-#else
-  auto compute = [&](const char* sa, const char* sb, int shift) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      bf16x8_t fa[TM], fb[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = arow + i * 32 + shift;
-        const int chunk = 2 * s + ah;
-        fa[i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(sa + row * 128 + ((chunk ^ Geo<BM>::swz(row)) << 4)));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) fb[j] = frag_read<BN, HTRVT_KMAJOR>(sb, wn * TN + j, s, lane);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-  };
-#endif
-
-  int gdy = 0, gcc = 0;           // group g
-  for (int g = 0; g < NG; ++g) {
-    int ndy = gdy, ncc = gcc + 1;   // group g + 1
-    if (ncc == NC) {
-      ncc = 0;
-      ++ndy;
-    }
-    const bool nvalid = g + 1 < NG;
-    const char* sa = smem + (g & 1) * H::A_STAGE;
-    const int nast = (g + 1) & 1;
-    // ---- k-tile 3g (dx = 0): B(3g+2) = (g, dx 2) -> stage 2; first half of halo(g+1) ----
-    if (!consumer) {
-      issueB(2, gdy, gcc, 2, true);
-      issueA(0, nast, ndy, ncc, nvalid);
-    } else {
-      compute(sa, smem + H::B_BASE + 0 * H::B_STAGE, DGRAD ? 2 : 0);
-    }
-    if (!consumer) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B + H::NP_AH) : "memory");
-    __builtin_amdgcn_s_barrier();
-    // ---- k-tile 3g+1 (dx = 1): B(3g+3) = (g+1, dx 0) -> stage 0; second half of halo(g+1) ----
-    if (!consumer) {
-      issueB(0, ndy, ncc, 0, nvalid);
-      issueA(1, nast, ndy, ncc, nvalid);
-    } else {
-      compute(sa, smem + H::B_BASE + 1 * H::B_STAGE, 1);
-    }
-    if (!consumer) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B + H::NP_AH) : "memory");
-    __builtin_amdgcn_s_barrier();
-    // ---- k-tile 3g+2 (dx = 2): B(3g+4) = (g+1, dx 1) -> stage 1 ----
-    if (!consumer) {
-      issueB(1, ndy, ncc, 1, nvalid);
-    } else {
-      compute(sa, smem + H::B_BASE + 2 * H::B_STAGE, DGRAD ? 0 : 2);
-    }
-    if (!consumer) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B) : "memory");
-    __builtin_amdgcn_s_barrier();
-    gdy = ndy;
-    gcc = ncc;
-  }
-  if (!consumer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-fill pieces issued past the last k-tile
-  __builtin_amdgcn_s_barrier();
-
-#ifndef HTRVT_HALO_MFMA32
-  halo_acc16_to_32<TM, TN>(acc, a4);
-  epilogue_staged<TN, BN, BM, NW_TOTAL, DGRAD, !DGRAD, P, 16>(acc, p, 0ll, m0, n0, wm, wn, tile_m, lane, wave, smem, consumer);
-#else
-  epilogue_staged<TN, BN, BM, NW_TOTAL, DGRAD, !DGRAD>(acc, p, 0ll, m0, n0, wm, wn, tile_m, lane, wave, smem, consumer);
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -747,13 +587,15 @@ int launch_halo_fs2(const KParams& p, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// gemm_halo_body, round 5: consumer and loader waves run SEPARATE copies of the loop (same barriers) -- straight-line fragment
-// reads + MFMAs between barriers on one side, nothing but address arithmetic and DMA issue on the other.  In the one-loop form
-// above every wave walked both sides' branches and the register allocation, the scalar state and the instruction stream of
-// either role carried the other's: same-box A/B -5 ... -9 % per launch on every stride-1 3x3 convolution of the stem
-// (profiles/r05_experiments.md).  The epilogue is inlined once per role (the loader copy with a dead accumulator set).
+// gemm_halo_body: consumer and loader waves run SEPARATE copies of the loop (same barriers) -- straight-line fragment reads +
+// MFMAs between barriers on one side, nothing but address arithmetic and DMA issue on the other.  In one loop walked by every
+// wave, the register allocation, the scalar state and the instruction stream of either role carried the other's: the split
+// form is -5 ... -9 % per launch on every stride-1 3x3 convolution of the stem (profiles/r05_experiments.md).  The epilogue is
+// inlined once per role (the loader copy with a dead accumulator set).
 // ---------------------------------------------------------------------------------------------
-// (DGRAD / forward and the row stride as in gemm_halo_body_oneloop above)
+// DGRAD = false: A rows = output pixels, source = x [B,H,W,Ci];  true: A rows = input pixels, source = dy [B,H,W,Co].
+// Forward with a row stride (sh = 2, W stride 1: the first conv of layer 1): M rows are OUTPUT rows, Hm = Ho of them per image,
+// and kernel row gdy of output row h reads input row h * sh + gdy - 1; dgrad is served at stride 1 only.
 template <int BN, bool DGRAD, bool F32, class P>
 __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
   using H = HaloGeo<BN>;
@@ -778,15 +620,12 @@ __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
 
   if (wave < NWC) {
     // ================================ consumer waves: fragments + MFMA, nothing else ================================
-    HTRVT_STAMP(0);
     f32x4h_t a4[2 * TM][2 * TN];
 #pragma unroll
     for (int i = 0; i < 2 * TM; ++i)
 #pragma unroll
       for (int j = 0; j < 2 * TN; ++j) a4[i][j] = f32x4h_t{0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_s_barrier();
-    HTRVT_STAMP(1);
-    HTRVT_STAMP(2);
     for (int g = 0; g < NG; ++g) {
       const char* sa = smem + (g & 1) * H::A_STAGE;
       halo_mma16<BN, TM, TN>(a4, sa, smem + H::B_BASE + 0 * H::B_STAGE, DGRAD ? 2 : 0, wm, wn, lane);
@@ -797,7 +636,6 @@ __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
       __builtin_amdgcn_s_barrier();
     }
     __builtin_amdgcn_s_barrier();
-    HTRVT_STAMP(3);
     if constexpr (F32) {
       halo_epilogue_f32<BN, TM, TN, NW_TOTAL * 64, !DGRAD>(a4, p, m0, n0, wm, wn, tile_m, lane, smem, true);
     } else {
@@ -805,16 +643,6 @@ __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
       halo_acc16_to_32<TM, TN>(acc, a4);
       epilogue_staged<TN, BN, BM, NW_TOTAL, DGRAD, !DGRAD, P, 16>(acc, p, 0ll, m0, n0, wm, wn, tile_m, lane, wave, smem, true);
     }
-    HTRVT_STAMP(6);
-#ifdef HTRVT_EXP_STAMP      // experiment builds: when have this wave's stores drained, and on which CU did the tile run
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    HTRVT_STAMP(7);
-    if (threadIdx.x == 0 && blockIdx.x < 8192) {
-      unsigned hw;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      htrvt_dbg[blockIdx.x * 16 + 8] = hw;
-    }
-#endif
   } else {
     // ================================ loader waves: LDS-DMA of the operands, then the side tile ================================
     const int lw = (wave - NWC) & 3;
@@ -907,11 +735,7 @@ __global__ __launch_bounds__(768) void gemm_halo_kernel(const KParams p) {
   typedef const __attribute__((address_space(4))) KParams KP;
   (void)p;
   KP* kp = (KP*)__builtin_amdgcn_kernarg_segment_ptr();
-#ifdef HTRVT_HALO_ONELOOP      // A/B builds: consumer and loader waves in ONE copy of the loop (rounds 3-4)
-  gemm_halo_body_oneloop<BN, DGRAD>(*kp, (int)blockIdx.x);
-#else
   gemm_halo_body<BN, DGRAD, F32>(*kp, (int)blockIdx.x);
-#endif
 }
 
 template <int BN, bool DGRAD, bool F32 = false>

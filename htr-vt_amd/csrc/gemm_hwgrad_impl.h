@@ -540,7 +540,7 @@ int launch_hwgrad16(const KParams& p, int zdim, hipStream_t st) {
   }
   const int ntiles = 3 * (p.Cpad / CC) * p.tiles_n;
   dim3 grid(ntiles, 1, zdim);
-  if (p.split_k > 1 && ((p.split_k & 7) == 0 || hwgrad_xcd_ranges())) grid = dim3(p.split_k * ntiles, 1, 1);
+  if (p.split_k > 1) grid = dim3(p.split_k * ntiles, 1, 1);
   hipLaunchKernelGGL(kern, grid, dim3(768), H::LDS_BYTES, st, p);
   if (SW == 1) set_last_kernel("gemm_hwgrad16_kernel<%d, %d>", CC, BN);
   else set_last_kernel("gemm_hwgrad16_kernel<%d, %d, %d>", CC, BN, SW);
@@ -571,7 +571,7 @@ int launch_hwgrad(const KParams& p, int zdim, hipStream_t st) {
   }
   const int ntiles = (PAIR ? (3 * (p.Cpad / 64) + 1) / 2 : 3 * (p.Cpad / CC)) * p.tiles_n;
   dim3 grid(ntiles, 1, zdim);
-  if (p.split_k > 1 && ((p.split_k & 7) == 0 || hwgrad_xcd_ranges())) grid = dim3(p.split_k * ntiles, 1, 1);
+  if (p.split_k > 1) grid = dim3(p.split_k * ntiles, 1, 1);
   hipLaunchKernelGGL(kern, grid, dim3(768), H::LDS_BYTES, st, p);
   set_last_kernel(PAIR ? "gemm_hwgrad_kernel<%d, %d, true>" : "gemm_hwgrad_kernel<%d, %d>", CC, BN);
   const int rc = check_launch("gemm_hwgrad_kernel");

@@ -16,15 +16,6 @@ namespace {
 
 constexpr int NT = 256;
 
-// HTRVT_STEM_VALU=1: keep the float32-FMA stem kernel on the bfloat16 path too (A/B runs, tests of that kernel)
-bool stem_force_valu() {
-  static const bool v = [] {
-    const char* e = getenv("HTRVT_STEM_VALU");
-    return e != nullptr && e[0] == '1';
-  }();
-  return v;
-}
-
 // ------------------------------------------------------------------ img_stats
 // one block of 1024 threads per image; two passes (mean, then centred variance) -> {mean, rstd}; four 16-byte loads in
 // flight per thread (256 threads with one load in flight each were a chain of 2 x 64 round trips: 53 us for 34 MB)
@@ -562,7 +553,7 @@ __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, con
 // stride (per element loads from global and a 64-bit modulo per vector were most of the kernel's instructions).
 // MASK (bfloat16, 8 elements per vector): byte i of `mask` = the signs of vector i's outputs, bit j set where y[8 i + j] > 0
 // -- the ReLU's backward reads this bit instead of y (HtrvtGemmDesc.relu_bits).
-// STREAM: inputs by non-temporal loads, for activations of >= bn_stream_bytes() (common.h)
+// STREAM: inputs by non-temporal loads, for activations of >= BN_STREAM_BYTES (common.h)
 template <typename T, int RES, bool MASK = false, bool STREAM = false>  // RES: 0 none, 1 identity residual, 2 residual with its own BN coefficients
 __global__ __launch_bounds__(NT) void bn_apply_kernel(const T* __restrict__ x, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, const T* __restrict__ res,
@@ -812,7 +803,7 @@ extern "C" int htrvt_stem_fwd(const void* img, const float* stats, const float* 
   HTRVT_REQUIRE(img && stats && w && scale && shift && y, "htrvt_stem_fwd: null argument");
   HTRVT_REQUIRE(C % ch == 0 && C / ch <= NT && H % 2 == 0 && H >= 4, "htrvt_stem_fwd: C=%d must be a multiple of %d and <= %d", C,
                 ch, NT * ch);
-  if (dtype == HTRVT_BF16 && !stem_force_valu()) {   // conv1 as an MFMA product, pooling in the accumulator layout (stem_mfma.hip)
+  if (dtype == HTRVT_BF16) {   // conv1 as an MFMA product, pooling in the accumulator layout (stem_mfma.hip); refused shapes fall through
     const int r = stem_mfma_try_launch(img, stats, w, scale, shift, y, idx, B, H, W, C, img_u8, (hipStream_t)stream);
     if (r != 0) return r < 0 ? r : 0;
   }
@@ -871,7 +862,7 @@ extern "C" int htrvt_bn_apply(const void* x, const float* scale, const float* sh
   hipStream_t st = (hipStream_t)stream;
 #define LAUNCH_BN_APPLY(T, R)                                                                                            \
   do {                                                                                                                   \
-  if (nvec * 16 >= bn_stream_bytes())                                                                                    \
+  if (nvec * 16 >= BN_STREAM_BYTES)                                                                                      \
     hipLaunchKernelGGL((bn_apply_kernel<T, R, false, true>), grid, dim3(NT), (size_t)(R == 2 ? 4 : 2) * C * sizeof(float), st, (const T*)x, scale, shift, (const T*)res, rscale, \
                        rshift, (T*)y, nvec, C, relu);                                                                    \
   else                                                                                                                   \
@@ -902,7 +893,7 @@ extern "C" int htrvt_bn_apply_mask(const void* x, const float* scale, const floa
   hipStream_t st = (hipStream_t)stream;
 #define LAUNCH_BN_APPLY_MASK(R)                                                                                              \
   do {                                                                                                                       \
-  if (nvec * 16 >= bn_stream_bytes())                                                                                        \
+  if (nvec * 16 >= BN_STREAM_BYTES)                                                                                          \
     hipLaunchKernelGGL((bn_apply_kernel<bf16_t, R, true, true>), grid, dim3(NT), (size_t)(R == 2 ? 4 : 2) * C * sizeof(float), st, \
                        (const bf16_t*)x, scale, shift, (const bf16_t*)res, rscale, rshift, (bf16_t*)y, nvec, C, relu, mask);  \
   else                                                                                                                       \

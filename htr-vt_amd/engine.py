@@ -14,8 +14,6 @@ from __future__ import annotations
 
 import math
 
-import os
-
 import torch
 
 from . import ops
@@ -132,25 +130,12 @@ class Engine:
         # they may run on separate streams -- an epilogue-only class (no tap reaches it) then overlaps an MFMA-heavy one
         self.parallel_classes = False
         self._cls_streams = None
-        # training steps rewrite every weight: re-pack / re-cast all of them on the side stream at the start of the forward,
-        # under the (HBM-bound) image statistics, conv1 and max-pool kernels, instead of ~30 latency-bound launches in
-        # front of their first use
-        self.prefetch_packs = True
         # bf16: every conv / Linear weight is re-packed by ONE table-driven launch per step and the conv weight gradients are
         # unpacked by one launch per DP bucket (csrc/relayout.hip) instead of one launch per tensor (47 per step)
         self.table_relayout = True
-        self.relu_bitmask = True        # a block's output ReLU: the forward BatchNorm pass writes its 1-bit mask, the fused dgrad reads that instead of the activation
         self.relu_mask_from_bn = True   # conv2's fused dgrad epilogue: ReLU mask from the BatchNorm input it reads anyway (no read of a1)
         self.merge_bn_backward = True   # first block of a stage: bn2 + downsample-BN backward in one pass over the shared gradient
         self._pending_unpack = []
-        # first block of a stage, bf16: the input gradient of the 1x1 downsample conv is formed INSIDE the class-(0,0) launch
-        # of the strided 3x3 conv's dgrad (one more tap, HtrvtGemmDesc.A2) instead of by its own parity-class launches
-        # plus a residual round trip of the whole input gradient
-        self.fuse_downsample_dgrad = True
-        self.halo_wgrad = True         # 3x3 stride-1 conv weight gradients on the halo-staged kernel (csrc/gemm_hwgrad_impl.h)
-        # strided 3x3 conv dgrad: all parity classes in ONE launch on halo-staged tiles (csrc/gemm_halo_impl.h,
-        # gemm_halo_s2_kernel) instead of one gather launch per class
-        self.merged_strided_dgrad = True
         # split-K weight gradients through per-K-range slabs + an ordered sum instead of float atomics: bitwise reproducible
         # run to run (tests/test_determinism_gpu.py).  Round 3: also the bf16 default -- equal to the atomic form at 64-128
         # images per GPU (36.39 vs 36.41 ms), faster below (B = 32: 11.33 vs 11.48 ms, B = 16: 7.22 vs 7.57 ms: float atomics
@@ -166,12 +151,6 @@ class Engine:
         self.saved = None
         self._bn_train = True
         self._zarena, self._zoff, self._zneed, self._zneed_max = None, None, 0, 0
-        # A/B runs on one box: HTRVT_ENGINE_OVERRIDE="relu_mask_from_bn=0,table_relayout=0" flips boolean switches above
-        for kv in filter(None, os.environ.get("HTRVT_ENGINE_OVERRIDE", "").split(",")):
-            k, _, v = kv.partition("=")
-            if not isinstance(getattr(self, k.strip(), None), bool):
-                raise ValueError(f"HTRVT_ENGINE_OVERRIDE: no boolean engine switch {k!r}")
-            setattr(self, k.strip(), v.strip() not in ("0", "false", "False", ""))
 
     # ------------------------------------------------------------------ small helpers
     def _empty(self, *shape, dtype=None):
@@ -411,10 +390,10 @@ class Engine:
         return dx
 
     def _hwgrad_tiles(self, g):
-        """(workgroups per pixel range, tile rows, tile columns) of the halo-staged conv weight-gradient kernel, asked of the
-        library itself (htrvt_gemm_wgrad_tiling: the same eligibility test htrvt_gemm applies), or None where the generic
-        kernel serves the convolution"""
-        if self.gdt != torch.bfloat16 or not self.halo_wgrad:
+        """(workgroups per pixel range, tile rows, tile columns) of the halo-staged conv weight-gradient kernel
+        (csrc/gemm_hwgrad_impl.h: 3x3 stride-1 convolutions), asked of the library itself (htrvt_gemm_wgrad_tiling: the same
+        eligibility test htrvt_gemm applies), or None where the generic kernel serves the convolution"""
+        if self.gdt != torch.bfloat16:
             return None
         import ctypes
         from ._lib import GemmDesc
@@ -443,12 +422,13 @@ class Engine:
         # multiples of 8 let the kernel keep all tiles of one K range on one XCD (shared L2); small factors otherwise
         # a single output tile (the 1x1 downsample weight gradients, K = 1 M pixels at layer 1): up to one K range per CU
         smax = 257 if tiles == 1 else 129
-        # round 5: the split-K kernels keep the (range, tile) pairs of one XCD consecutive for ANY split factor (xcd_range_map,
-        # csrc/gemm_dma_impl.h), so every factor up to 64 is a candidate for the conv / MN-major launches, not only the multiples
-        # of 8 and a hand-picked few; HTRVT_SPLITK_LEGACY=1 restores the former candidate list and its 10 % penalty (A/B runs)
-        legacy = os.environ.get("HTRVT_SPLITK_LEGACY", "0") == "1" or os.environ.get("HTRVT_NO_XCD_RANGES", "0") == "1"
+        # The conv weight-gradient kernels (gemm_dma_kernel and the gemm_hwgrad kernels) keep the (range, tile) pairs of one XCD
+        # consecutive for ANY split factor (xcd_range_map, csrc/gemm_dma_impl.h), so every factor up to 64 is a candidate for
+        # them, not only the multiples of 8 and a hand-picked few.  The list is widened for a `tiling` without `conv` too, i.e.
+        # the MN-major 8-phase Linear weight-gradient kernel (csrc/gemm8pt_impl.h), which still deals its K ranges over the
+        # plain z-grid: there the widened list is unmeasured.
         cands = [1, 2, 3, 4, 5, 6, 7] + list(range(8, smax, 8)) + ([10, 12, 14, 20, 28] if tiling is not None else [])
-        if not legacy and (conv or tiling is not None):
+        if conv or tiling is not None:
             cands = sorted(set(cands) | set(range(8, 65)))
         for s in cands:
             if Kred // s < 512:
@@ -458,7 +438,7 @@ class Engine:
             # every block's float32 output tile: atomics ~1.3 TB/s chip-wide; slabs are written and read back once at HBM speed
             t = flops / 1.0e15 * (rounds * 256.0 / blocks) + blocks * bm * bn * 4 / (2.5e12 if self.deterministic and s > 1 else 1.3e12)
             if s > 1 and s % 8:
-                t *= 1.10 if legacy else 1.02     # (legacy: no XCD grouping of the K ranges, 4-7x the operand traffic; now: a range may straddle two XCDs)
+                t *= 1.02     # a K range may straddle two XCDs
             if best_t is None or t < best_t:
                 best, best_t = s, t
         return best
@@ -509,7 +489,7 @@ class Engine:
         tiling = None
         if self.gdt == torch.bfloat16 and self.deterministic and not plain:
             # the MN-major 8-phase kernel's 256 x 256 tiles where the LIBRARY says it serves the launch (htrvt_gemm_wgrad_tiling:
-            # gemm8pt_serves -- alignment, 2 GiB, the HTRVT_NO_MNMAJOR_8PHASE switch; no copy of that test here)
+            # gemm8pt_serves -- alignment, 2 GiB; no copy of that test here)
             import ctypes
             from ._lib import GemmDesc
             d = GemmDesc()
@@ -579,8 +559,9 @@ class Engine:
 
     def _dgrad_merged(self, g, dy=None, wd=None, dx=None, extra=None):
         """M tiles of the merged strided-dgrad launch (HtrvtGemmDesc.cls_h = -2) when the library serves `g` in that form
-        (asked of the library itself: htrvt_gemm_dgrad_merged_tiles), else 0"""
-        if not (self.merged_strided_dgrad and self.gdt == torch.bfloat16 and not self.split and self._dgrad_by_class(g) and g.kh == 3):
+        (asked of the library itself: htrvt_gemm_dgrad_merged_tiles), else 0.  All parity classes of a strided 3x3 conv dgrad
+        in ONE launch on halo-staged tiles (csrc/gemm_halo_impl.h, gemm_halo_s2_kernel) instead of one gather launch per class"""
+        if not (self.gdt == torch.bfloat16 and not self.split and self._dgrad_by_class(g) and g.kh == 3):
             return 0
         import ctypes
         from ._lib import GemmDesc
@@ -756,7 +737,7 @@ class Engine:
                                                    torch.zeros(Ci, taps, cpo, dtype=self.dtype, device=self.dev))
             jobs.append(_job(RELAYOUT_PACK_CONV, w, bufs[0], bufs[1], Co, Ci, taps, cpi, cpo, taps, 0))
             fresh.append((name, key, bufs))
-        if save and self.fuse_downsample_dgrad:
+        if save:
             for li in (1, 2, 3):
                 pb = f"patch_embed.layer{li}.0"
                 w3, wd = P[pb + ".conv1.weight"], P[pb + ".downsample.0.weight"]
@@ -928,10 +909,13 @@ class Engine:
             if not keep.is_cuda:    # through pinned memory: a pageable copy would make the host wait for the previous step
                 keep = keep.pin_memory().to(self.dev, non_blocking=True)
 
+        # training steps rewrite every weight: re-pack / re-cast all of them on the side stream at the start of the forward,
+        # under the (HBM-bound) image statistics, conv1 and max-pool kernels, instead of ~30 latency-bound launches in
+        # front of their first use
         prefetched = False
-        if self.prefetch_packs and self.dtype == torch.bfloat16 and self.single_stream:
+        if self.dtype == torch.bfloat16 and self.single_stream:
             self._repack_all(P, save) if self.table_relayout else None
-        elif self.prefetch_packs and self.dtype == torch.bfloat16:
+        elif self.dtype == torch.bfloat16:
             if self._side is None:
                 self._side = torch.cuda.Stream(device=self.dev)
             self._side.wait_stream(torch.cuda.current_stream())     # behind whatever wrote the weights (the optimizer step)
@@ -941,7 +925,7 @@ class Engine:
                 else:
                     for name, _ci, _co, _k, _st, _pd in s.stem_convs():
                         self._conv_w(name, P[name + ".weight"])
-                    if save and self.fuse_downsample_dgrad:
+                    if save:
                         for li in (1, 2, 3):
                             pb = f"patch_embed.layer{li}.0"
                             self._conv_w_joint_dgrad(pb + ".conv1", P[pb + ".conv1.weight"], pb + ".downsample.0", P[pb + ".downsample.0.weight"])
@@ -1030,8 +1014,9 @@ class Engine:
                 else:
                     gd, cd, bn_d = None, None, None
                     res_kw = dict(res=x)
-                # the block's output ReLU: its backward (fused into the NEXT block's conv1 dgrad) reads one bit per element
-                want_mask = bool(save and self.relu_bitmask and self.fuse_bn_backward and self.dtype == torch.bfloat16 and planes % 8 == 0)
+                # the block's output ReLU: the forward BatchNorm pass writes its 1-bit mask, and its backward (fused into the
+                # NEXT block's conv1 dgrad) reads that instead of the activation
+                want_mask = bool(save and self.fuse_bn_backward and self.dtype == torch.bfloat16 and planes % 8 == 0)
                 out = self.bn_apply(cb, bn_b[0], bn_b[1], relu=True, want_mask=want_mask, **res_kw)
                 out, omask = out if want_mask else (out, None)
                 if save:
@@ -1338,9 +1323,10 @@ class Engine:
             else:               # dout is already g = dOut * (out > 0) and the sums exist
                 gm = dout
                 parts_d = parts[1] if len(parts) > 1 else None
-            # downsample gradient as one more tap of the strided conv's class-(0,0) dgrad: d(conv1 out) and d(downsample
+            # downsample gradient as one more tap of the strided conv's class-(0,0) dgrad (HtrvtGemmDesc.A2) instead of its own
+            # parity-class launches plus a residual round trip of the whole input gradient: d(conv1 out) and d(downsample
             # out) then live back to back in one allocation (the second gather source sits at a fixed offset from the first)
-            fuse_ds = (self.fuse_downsample_dgrad and not self.split and blk["gd"] is not None and self._dgrad_by_class(blk["g1"]) and
+            fuse_ds = (not self.split and blk["gd"] is not None and self._dgrad_by_class(blk["g1"]) and
                        2 * blk["ca"].numel() * blk["ca"].element_size() < 2 ** 31 - 64)     # A2 lies behind A inside ONE 2 GiB descriptor
             pair = self._empty(2, *blk["ca"].shape) if fuse_ds else None
             dca_out = pair[0] if fuse_ds else None

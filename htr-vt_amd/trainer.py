@@ -275,9 +275,7 @@ class GraphedStep:
 
     @staticmethod
     def _engine_plan(eng):
-        import os
-        return (tuple(sorted((k, v) for k, v in vars(eng).items() if isinstance(v, bool) and k not in ("capturing", "single_stream", "_side_active", "_bn_train", "_saving"))),
-                os.environ.get("HTRVT_ENGINE_OVERRIDE", ""))
+        return tuple(sorted((k, v) for k, v in vars(eng).items() if isinstance(v, bool) and k not in ("capturing", "single_stream", "_side_active", "_bn_train", "_saving")))
 
     def step(self, img, targets, lengths, keep_mask=None, lr=None):
         """one replay; returns the (device, reused) mean-loss tensor of this step"""

@@ -2,8 +2,7 @@
 """Per-launch time of the table-driven relative-position attention (csrc/attn_relpos.hip) against the dense-bias route
 (htrvt_relpos_bias_fwd + the BIAS flavour of csrc/attention.hip forward; its backward with float atomics into a dense
 d(bias) + htrvt_relpos_bias_bwd), B = 128, h = 6, hd = 128.  One JSON line per shape.
-    python tools/bench_relpos.py [--iters 50]
-HTRVT_NO_RELPOS_SKIP=1 turns off the skipping of key / query tiles nobody in a workgroup can see (windowed blocks)."""
+    python tools/bench_relpos.py [--iters 50]"""
 import argparse
 import json
 import os

@@ -26,8 +26,7 @@ timeout -k 10 300 python bench.py --full --sam --no-cpu-baseline --no-parity-pat
 timeout -k 10 300 python bench.py --full --dtype split_bf16 --steps 3 --warmup 3 --no-cpu-baseline --no-parity-path > $O/split_bf16.json 2> $O/split_bf16.err; echo "split rc=$?"
 for b in 128 16; do timeout -k 10 300 python bench.py --full --batch $b --steps 10 --warmup 3 --no-cpu-baseline --no-parity-path --graph on > $O/graph_b$b.json 2> $O/graph_b$b.err; echo "graph b$b rc=$?"; done
 fi
-if [ "$PART" = "ab" ]; then      # same-box A/B against the previous round's tree (tools/r05_ab.sh) + the convolution / encoder micro-benchmarks
-bash tools/r05_ab.sh $TAG
+if [ "$PART" = "ab" ]; then      # the convolution / encoder micro-benchmarks
 timeout -k 10 300 python tools/bench_gemm.py --only "s1conv sconv c1x1" --rounds 2 > $O/conv_table.log 2>&1; echo "conv table rc=$?"
 timeout -k 10 300 python tools/bench_gemm.py --only enc --tiles 9 0 --rounds 2 > $O/enc_ab.log 2>&1; echo "enc ab rc=$?"
 exit 0
