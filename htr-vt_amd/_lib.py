@@ -135,6 +135,14 @@ PROTOTYPES = {
     "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "htrvt_sgm_xent_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "htrvt_sgm_convert": (i32, [vp, i32, vp, i32, i64, i32, vp]),
+    "htrvt_attn_local_supported": (i32, [i32, i32, i32]),
+    "htrvt_attn_local_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "htrvt_attn_local_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "htrvt_lgp_pool_norm_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
+    "htrvt_lgp_pool_norm_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "htrvt_lgp_upsample_fwd": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "htrvt_lgp_upsample_bwd_workspace_floats": (i64, [i32, i32]),
+    "htrvt_lgp_upsample_bwd": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
 }
 
 

@@ -46,12 +46,17 @@ class ModelShape:
     """Static shape of one model (mirrors MaskedAutoencoderViT.__init__, HTR_VT.py:143-172)."""
 
     def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS,
-                 pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False):
+                 pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False, lgp=None, pos_table=None):
         """The switches of the window-attention fork (model_window/model/HTR_VT.py), defaults = model_v1:
         pos_embed: tokens get the absolute position embedding; whiten_logits: the parameter-free LayerNorm over the logits;
         relpos: None, or per block (window, shift) -- attention with the block's relative-position table
         `blocks.{i}.attn.relative_position_bias_table` [2 table_patches - 1, heads] (window 0: full attention);
-        dropout: the model has dropout / drop-path in train mode (not implemented: a train-mode forward is refused)."""
+        dropout: the model has dropout / drop-path in train mode (not implemented: a train-mode forward is refused).
+        The LGP fork (model_lgp/model/plg.py), default None = the blocks above:
+        lgp: (window, g_tokens, branch_eps) -- every block is a LocalGlobalParallelBlockSimple: window attention over
+        `window` tokens beside attention over min(g_tokens, N) pooled tokens (their LayerNorm without affine at branch_eps),
+        fused by a Linear(2D, D); pos_table: float32 [N, D] position embedding the model supplies (the fork keeps it in a
+        non-persistent buffer, so no state dict carries it); the token count is what the stem leaves, as for relpos."""
         self.nb_cls = int(nb_cls)
         self.pos_embed, self.whiten_logits, self.dropout = bool(pos_embed), bool(whiten_logits), bool(dropout)
         self.relpos = None if relpos is None else [None if g is None else (int(g[0]), int(g[1])) for g in relpos]
@@ -63,7 +68,14 @@ class ModelShape:
         self.grid = (self.H // patch_size[0], self.W // patch_size[1])
         self.num_patches = self.grid[0] * self.grid[1]
         assert self.D % 32 == 0 and self.D % self.heads == 0
-        if self.relpos is None:
+        self.lgp = None if lgp is None else (int(lgp[0]), int(lgp[1]), float(lgp[2]))
+        self.pos_table = pos_table
+        if self.lgp is not None:
+            assert self.relpos is None and pos_table is not None
+            assert self.H % 64 == 0 and self.W % 8 == 0, "img_size: H a multiple of 64, W of 8"
+            self.num_patches = stem_tokens(self.H, self.W)
+            assert tuple(pos_table.shape) == (self.num_patches, self.D) and pos_table.dtype == torch.float32
+        elif self.relpos is None:
             assert self.H % 64 == 0 and self.W % 64 == 0, "img_size must be a multiple of 64 (HTR_VT.py:158-160)"
         else:   # the window fork has no position grid: the token count is what the stem leaves (any W multiple of 8)
             assert len(self.relpos) == self.depth
@@ -88,8 +100,10 @@ class ModelShape:
 
     def linears(self):
         names = []
+        attn = ["attn.qkv", "attn.proj"] if self.lgp is None else ["local_attn.qkv", "local_attn.proj", "global_attn.qkv",
+                                                                  "global_attn.proj", "fuse"]
         for i in range(self.depth):
-            names += [f"blocks.{i}.attn.qkv", f"blocks.{i}.attn.proj", f"blocks.{i}.mlp.fc1", f"blocks.{i}.mlp.fc2"]
+            names += [f"blocks.{i}.{n}" for n in attn + ["mlp.fc1", "mlp.fc2"]]
         return names + ["head"]
 
 
@@ -112,6 +126,8 @@ class Engine:
         # accumulate).  `gdt` is the element type the big GEMMs' operands have.
         self.split = bool(split_bf16)
         assert not self.split or dtype == torch.float32, "split_bf16 is a mode of the float32 path"
+        if self.split and shape.lgp is not None:
+            raise NotImplementedError("split_bf16 is not served for the LGP blocks: use torch.float32 (parity) or torch.bfloat16")
         self.gdt = torch.bfloat16 if self.split else dtype
         self._split_cache = []       # backward: the few most recent (source tensor, cat, hi, lo) splits (a gradient feeds dgrad AND wgrad)
         self._saved_planes, self._saving = {}, False    # forward(save=True): id(activation) -> its hi / lo planes, for the weight gradients
@@ -368,9 +384,14 @@ class Engine:
              residual=residual, c_f32=c_f32)
         return out
 
-    def linear_dgrad(self, dy, w, wt=None, act=0, preact=None, plain=False):
-        """dx[M,K] = dy[M,N] @ w[N,K]  (optionally * gelu'(preact)).  wt = w^T [K][>=N] (bf16 path): K-major B operand."""
+    def linear_dgrad(self, dy, w, wt=None, act=0, preact=None, plain=False, cols=None):
+        """dx[M,K] = dy[M,N] @ w[N,K]  (optionally * gelu'(preact)).  wt = w^T [K][>=N] (bf16 path): K-major B operand.
+        cols = (first, N): dy is that column block of a wider row-major tensor (not in split mode)."""
         M, N = dy.shape
+        ld, off = N, 0
+        if cols is not None:
+            assert not self.split
+            off, N = cols
         if self.split and not plain:      # wt = (hi | hi | lo) of w^T: [K][3 N]
             K = wt.shape[0]
             dx = self._empty(M, K)
@@ -384,9 +405,10 @@ class Engine:
         K = w.shape[1]
         dx = self._empty(M, K)
         if wt is not None:
-            gemm(dy, wt, dx, dtype=self.dtype, M=M, N=K, K=N, lda=N, ldb=wt.shape[1], ldc=K, act=act, preact=preact)
+            gemm(dy, wt, dx, dtype=self.dtype, M=M, N=K, K=N, lda=ld, ldb=wt.shape[1], ldc=K, act=act, preact=preact, a_off=off)
         else:
-            gemm(dy, w, dx, dtype=self.dtype, M=M, N=K, K=N, lda=N, ldb=K, ldc=K, b_layout=MNMAJOR, act=act, preact=preact)
+            gemm(dy, w, dx, dtype=self.dtype, M=M, N=K, K=N, lda=ld, ldb=K, ldc=K, b_layout=MNMAJOR, act=act, preact=preact,
+                 a_off=off)
         return dx
 
     def _hwgrad_tiles(self, g):
@@ -476,16 +498,22 @@ class Engine:
         if self._side is not None and self._side_active:
             torch.cuda.current_stream().wait_stream(self._side)
 
-    def linear_wgrad(self, dy, x, dw, dbias, plain=False):
-        return self._on_side(lambda: self._linear_wgrad(dy, x, dw, dbias, plain), dy, x)
+    def linear_wgrad(self, dy, x, dw, dbias, plain=False, cols=None):
+        return self._on_side(lambda: self._linear_wgrad(dy, x, dw, dbias, plain, cols), dy, x)
 
     def conv_wgrad(self, dy, x, g, dw):
         return self._on_side(lambda: self._conv_wgrad(dy, x, g, dw), dy, x)
 
-    def _linear_wgrad(self, dy, x, dw, dbias, plain=False):
-        """dw[N,K] += dy^T x ; dbias[N] += colsum(dy)."""
+    def _linear_wgrad(self, dy, x, dw, dbias, plain=False, cols=None):
+        """dw[N,K] += dy^T x ; dbias[N] += colsum(dy).  cols = (first, N): dy is that column block of a wider row-major
+        tensor (not in split mode)."""
         M, N = dy.shape
         K = x.shape[1]
+        ld, off = N, 0
+        if cols is not None:
+            assert not self.split
+            off, N = cols
+        dyp = dy.data_ptr() + off * dy.element_size()
         tiling = None
         if self.gdt == torch.bfloat16 and self.deterministic and not plain:
             # the MN-major 8-phase kernel's 256 x 256 tiles where the LIBRARY says it serves the launch (htrvt_gemm_wgrad_tiling:
@@ -494,9 +522,9 @@ class Engine:
             from ._lib import GemmDesc
             d = GemmDesc()
             d.dtype, d.a_layout, d.b_layout, d.gather = dt(self.gdt), MNMAJOR, MNMAJOR, 0
-            d.M, d.N, d.K, d.lda, d.ldb, d.ldc = N, K, M, (3 * N if self.split else N), K, K
+            d.M, d.N, d.K, d.lda, d.ldb, d.ldc = N, K, M, (3 * N if self.split else ld), K, K
             d.batch, d.split_k, d.c_f32, d.accumulate = 1, 2, 1, 1
-            d.A, d.B, d.C = ptr(dy), ptr(x), ptr(dw)
+            d.A, d.B, d.C = dyp, ptr(x), ptr(dw)
             tr_, tc_ = ctypes.c_int32(0), ctypes.c_int32(0)
             nt = lib.htrvt_gemm_wgrad_tiling(ctypes.byref(d), ctypes.byref(tr_), ctypes.byref(tc_))
             if nt > 0:
@@ -513,10 +541,10 @@ class Engine:
             if dbias is not None:
                 ops.colsum(dy, M, N, N, dbias, dti=self.dti)
             return
-        gemm(dy, x, dw, dtype=self.dtype, M=N, N=K, K=M, lda=N, ldb=K, ldc=K, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             split_k=sk, accumulate=True, c_f32=True, splitk_ws=self._splitk_ws(sk, N, K))
+        gemm(dy, x, dw, dtype=self.dtype, M=N, N=K, K=M, lda=ld, ldb=K, ldc=K, a_layout=MNMAJOR, b_layout=MNMAJOR,
+             split_k=sk, accumulate=True, c_f32=True, splitk_ws=self._splitk_ws(sk, N, K), a_off=off)
         if dbias is not None:
-            ops.colsum(dy, M, N, N, dbias, dti=self.dti)
+            ops.colsum(dyp, M, N, ld, dbias, dti=self.dti)
 
     def conv_fwd(self, x, wf, g: ConvGeom, want_stats, bn=None, relu=False, residual=None):
         """bn = (scale, shift): eval-mode BatchNorm (running statistics) folded into the launch -- C = relu?(conv * scale +
@@ -877,6 +905,8 @@ class Engine:
         if want_features and self.split:
             raise NotImplementedError("split_bf16 has no feature output: use compute_dtype=torch.float32 (parity) or "
                                       "torch.bfloat16")
+        if want_features and s.lgp is not None:
+            raise NotImplementedError("want_features is not served for the LGP model")
         if train and s.dropout:
             raise NotImplementedError("train-mode forward of a model with dropout / drop-path: not implemented (build the "
                                       "window model with create_model(..., dropout=False) to train without them)")
@@ -1031,7 +1061,11 @@ class Engine:
         assert N == s.num_patches, f"token count {N} != num_patches {s.num_patches}"
         D = s.D
         tok = self._empty(B, N, D)
-        if s.pos_embed:
+        if s.pos_table is not None:     # LGP fork: the model's own table (no state-dict entry)
+            if getattr(self, "_pos_table", None) is None:
+                self._pos_table = s.pos_table.to(self.dev).contiguous()
+            pos = self._pos_table
+        elif s.pos_embed:
             pos = P["pos_embed"].reshape(N, D)
         else:                       # window fork: no absolute position embedding (HTR_VT.py:265 of model_window)
             if getattr(self, "_zero_pos", None) is None or self._zero_pos.shape != (N, D):
@@ -1050,6 +1084,11 @@ class Engine:
         enc_saved = []
         for i in range(s.depth):
             p = f"blocks.{i}"
+            if s.lgp is not None:
+                e, xt = self._lgp_block_fwd(P, p, xt, B, N, save, st)
+                if save:
+                    enc_saved.append(e)
+                continue
             ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
             wq, _ = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             qkv = self.linear_fwd(ln1, wq, P[p + ".attn.qkv.bias"])
@@ -1057,23 +1096,13 @@ class Engine:
             geo = s.relpos[i] if s.relpos is not None else None
             if geo is not None:
                 Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st)
-            elif self.fused_attention and lib.htrvt_attn_supported(N, hd, self.dti):
-                # bf16: one launch, scores / probabilities stay on chip; lse2 is what the recomputing backward needs
-                Pm, lse = None, (self._empty(B * h, N, dtype=torch.float32) if save else None)
-                check(lib.htrvt_attn_fwd(ptr(qkv), None, ptr(O), ptr(lse), B, N, h, hd, scale, self.dti, st), "attn_fwd")
             else:
-                Pm, lse = self._attention_fwd_unfused(qkv, O, B, N, D, h, hd, scale, st), None
+                Pm, lse = self._attention_fwd(qkv, O, B, N, D, h, hd, scale, save, st)
             wp, _ = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             x1 = self.linear_fwd(O, wp, P[p + ".attn.proj.bias"], residual=xt)
-            ln2, m2, r2 = self.ln_fwd(x1, P[p + ".norm2.weight"], P[p + ".norm2.bias"], save)
-            w1_, _ = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
-            hpre = self._empty(M, s.hidden) if save else None
-            hact = self.linear_fwd(ln2, w1_, P[p + ".mlp.fc1.bias"], act=1, preact=hpre)
-            w2_, _ = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
-            x2 = self.linear_fwd(hact, w2_, P[p + ".mlp.fc2.bias"], residual=x1)
+            x2, mlp = self._mlp_fwd(P, p, x1, save)
             if save:
-                enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, ln2=ln2, m2=m2, r2=r2,
-                                      hpre=hpre, h=hact, geo=geo))
+                enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, geo=geo, **mlp))
             xt = x2
 
         # --- norm + head + sequence LayerNorm (HTR_VT.py:236-239) ---
@@ -1096,6 +1125,135 @@ class Engine:
             check(lib.htrvt_sgm_convert(ptr(xn), self.dti, ptr(feats), 0, M * D, 0, st), "sgm_convert")
             return y, feats
         return y
+
+    def _attention_fwd(self, qkv, O, B, N, D, h, hd, scale, save, st):
+        """full self-attention over N tokens: (P or None, lse2 or None) as the backward wants them"""
+        if self.fused_attention and lib.htrvt_attn_supported(N, hd, self.dti):
+            # bf16: one launch, scores / probabilities stay on chip; lse2 is what the recomputing backward needs
+            lse = self._empty(B * h, N, dtype=torch.float32) if save else None
+            check(lib.htrvt_attn_fwd(ptr(qkv), None, ptr(O), ptr(lse), B, N, h, hd, scale, self.dti, st), "attn_fwd")
+            return None, lse
+        return self._attention_fwd_unfused(qkv, O, B, N, D, h, hd, scale, st), None
+
+    def _attention_bwd(self, qkv, Pm, lse, O, dO, dqkv, B, N, D, h, hd, scale, st):
+        if Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
+            delta = self._empty(B * h, N, dtype=torch.float32)
+            check(lib.htrvt_attn_bwd(ptr(qkv), None, ptr(O), ptr(dO), ptr(lse), ptr(delta), ptr(dqkv), None,
+                                     B, N, h, hd, scale, self.dti, st), "attn_bwd")
+        else:
+            self._attention_bwd_unfused(qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st)
+
+    def _mlp_fwd(self, P, p, x1, save):
+        """x2 = x1 + fc2(gelu(fc1(norm2(x1)))); returns (x2, what the backward keeps)"""
+        ln2, m2, r2 = self.ln_fwd(x1, P[p + ".norm2.weight"], P[p + ".norm2.bias"], save)
+        w1_, _ = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
+        hpre = self._empty(x1.shape[0], self.s.hidden) if save else None
+        hact = self.linear_fwd(ln2, w1_, P[p + ".mlp.fc1.bias"], act=1, preact=hpre)
+        w2_, _ = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
+        x2 = self.linear_fwd(hact, w2_, P[p + ".mlp.fc2.bias"], residual=x1)
+        return x2, dict(ln2=ln2, m2=m2, r2=r2, hpre=hpre, h=hact)
+
+    def _mlp_bwd(self, P, G, e, dx):
+        """gradient of the block's x1 (MLP branch + residual) from the gradient of its output"""
+        p = e["p"]
+        w2_, w2t = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
+        dhpre = self.linear_dgrad(dx, w2_, w2t, act=2, preact=e["hpre"])
+        self.linear_wgrad(dx, e["h"], G[p + ".mlp.fc2.weight"], G[p + ".mlp.fc2.bias"])
+        w1_, w1t = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
+        dln2 = self.linear_dgrad(dhpre, w1_, w1t)
+        self.linear_wgrad(dhpre, e["ln2"], G[p + ".mlp.fc1.weight"], G[p + ".mlp.fc1.bias"])
+        del dhpre
+        return self.ln_bwd(dln2, e["x1"], e["m2"], e["r2"], P[p + ".norm2.weight"], dx, G[p + ".norm2.weight"],
+                           G[p + ".norm2.bias"])
+
+    # ------------------------------------------------------------------ the LGP fork's block (model_lgp/model/plg.py:172-212)
+    def _lgp_block_fwd(self, P, p, xt, B, N, save, st):
+        """x1 = x + fuse([local_attn(y) | global_attn(y)]), y = norm1(x); x2 = x1 + mlp(norm2(x1)).  The two branches write
+        the halves of one [B N][2D] buffer (no cat copy); csrc/lgp.hip has the window attention, the pooling + LayerNorm in
+        front of the global branch and the scaled up-sampling behind it, everything else is the kernels of the v1 block."""
+        s = self.s
+        D, h, hd, M = s.D, s.heads, s.hd, B * N
+        scale = hd ** -0.5
+        win, gtok, beps = s.lgp
+        Gt = min(gtok, N)
+        es = xt.element_size()
+        ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
+        cat = self._empty(M, 2 * D)
+        # local branch: qkv -> attention inside windows (padding slots = the qkv bias) -> proj into the left half
+        lb = P[p + ".local_attn.qkv.bias"]
+        wq, _ = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
+        qkv = self.linear_fwd(ln1, wq, lb)
+        O = self._empty(M, D)
+        check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(lb), ptr(O), B, N, h, hd, win, scale, self.dti, st), "attn_local_fwd")
+        wp, _ = self._lin_w(p + ".local_attn.proj", P[p + ".local_attn.proj.weight"])
+        gemm(O, wp, cat, dtype=self.dtype, M=M, N=D, K=D, lda=D, ldb=D, ldc=2 * D, bias=P[p + ".local_attn.proj.bias"])
+        # global branch: pool to Gt tokens + LayerNorm -> qkv -> full attention -> proj -> up-sample * sigmoid(alpha), right half
+        z = self._empty(B * Gt, D)
+        zmean, zrstd = self._empty(B * Gt, dtype=torch.float32), self._empty(B * Gt, dtype=torch.float32)
+        check(lib.htrvt_lgp_pool_norm_fwd(ptr(ln1), ptr(z), ptr(zmean), ptr(zrstd), B, N, Gt, D, beps, self.dti, st),
+              "lgp_pool_norm_fwd")
+        wgq, _ = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
+        qkvg = self.linear_fwd(z, wgq, P[p + ".global_attn.qkv.bias"])
+        Og = self._empty(B * Gt, D)
+        Pg, lseg = self._attention_fwd(qkvg, Og, B, Gt, D, h, hd, scale, save, st)
+        wgp, _ = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
+        yg = self.linear_fwd(Og, wgp, P[p + ".global_attn.proj.bias"])
+        check(lib.htrvt_lgp_upsample_fwd(ptr(yg), ptr(P[p + ".global_attn.logit_alpha"]), cat.data_ptr() + D * es, 2 * D,
+                                         B, N, Gt, D, self.dti, st), "lgp_upsample_fwd")
+        wf, _ = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
+        x1 = self.linear_fwd(cat, wf, P[p + ".fuse.bias"], residual=xt)
+        x2, mlp = self._mlp_fwd(P, p, x1, save)
+        e = None
+        if save:
+            e = dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, O=O, cat=cat, z=z, zrstd=zrstd, qkvg=qkvg, Pg=Pg, lseg=lseg,
+                     Og=Og, yg=yg, x1=x1, Gt=Gt, **mlp)
+        return e, x2
+
+    def _lgp_block_bwd(self, P, G, e, dx, B, N, st):
+        s = self.s
+        D, h, hd, M = s.D, s.heads, s.hd, B * N
+        scale = hd ** -0.5
+        win, Gt = s.lgp[0], e["Gt"]
+        p = e["p"]
+        dx1 = self._mlp_bwd(P, G, e, dx)
+        es = dx1.element_size()
+        wf, wft = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
+        dcat = self.linear_dgrad(dx1, wf, wft)                       # [M][2D]: left half d local proj, right half d global
+        self.linear_wgrad(dx1, e["cat"], G[p + ".fuse.weight"], G[p + ".fuse.bias"])
+        # global branch
+        alpha = P[p + ".global_attn.logit_alpha"]
+        dyg = self._empty(B * Gt, D)
+        ws = self._empty(lib.htrvt_lgp_upsample_bwd_workspace_floats(B, Gt), dtype=torch.float32)
+        check(lib.htrvt_lgp_upsample_bwd(dcat.data_ptr() + D * es, 2 * D, ptr(e["yg"]), ptr(alpha), ptr(dyg),
+                                         ptr(G[p + ".global_attn.logit_alpha"]), ptr(ws), B, N, Gt, D, self.dti, st),
+              "lgp_upsample_bwd")
+        wgp, wgpt = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
+        dOg = self.linear_dgrad(dyg, wgp, wgpt)
+        self.linear_wgrad(dyg, e["Og"], G[p + ".global_attn.proj.weight"], G[p + ".global_attn.proj.bias"])
+        dqkvg = self._empty(B * Gt, 3 * D)
+        self._attention_bwd(e["qkvg"], e["Pg"], e["lseg"], e["Og"], dOg, dqkvg, B, Gt, D, h, hd, scale, st)
+        wgq, wgqt = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
+        dz = self.linear_dgrad(dqkvg, wgq, wgqt)
+        self.linear_wgrad(dqkvg, e["z"], G[p + ".global_attn.qkv.weight"], G[p + ".global_attn.qkv.bias"])
+        # local branch
+        wp, wpt = self._lin_w(p + ".local_attn.proj", P[p + ".local_attn.proj.weight"])
+        dO = self.linear_dgrad(dcat, wp, wpt, cols=(0, D))
+        self.linear_wgrad(dcat, e["O"], G[p + ".local_attn.proj.weight"], G[p + ".local_attn.proj.bias"], cols=(0, D))
+        lb, glb = P[p + ".local_attn.qkv.bias"], G[p + ".local_attn.qkv.bias"]
+        dqkv = self._empty(M, 3 * D)
+        dpad = self._empty(B, 2 * D, dtype=torch.float32)
+        check(lib.htrvt_attn_local_bwd(ptr(e["qkv"]), ptr(lb), ptr(dO), ptr(dqkv), ptr(dpad), B, N, h, hd, win, scale, self.dti,
+                                       st), "attn_local_bwd")
+        wq, wqt = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
+        dln1 = self.linear_dgrad(dqkv, wq, wqt)
+        self.linear_wgrad(dqkv, e["ln1"], G[p + ".local_attn.qkv.weight"], glb)
+        if N % win:     # the padding rows' k / v gradient; on the weight-gradient stream, behind the bias column sum above
+            self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, glb.data_ptr() + 4 * D, dti=0), dpad)
+        ws2 = self._empty(2 * B * Gt, dtype=torch.float32)
+        check(lib.htrvt_lgp_pool_norm_bwd(ptr(dz), ptr(e["z"]), ptr(e["zrstd"]), ptr(ws2), ptr(dln1), B, N, Gt, D, 1, self.dti,
+                                          st), "lgp_pool_norm_bwd")
+        return self.ln_bwd(dln1, e["x0"], e["m1"], e["r1"], P[p + ".norm1.weight"], dx1, G[p + ".norm1.weight"],
+                           G[p + ".norm1.bias"])
 
     def _relpos_attention_fwd(self, P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st):
         """attention of a window-fork block with its relative-position table: bf16 on the table-driven fused kernels
@@ -1248,30 +1406,21 @@ class Engine:
 
         for e in reversed(sv["enc"]):
             p = e["p"]
+            if s.lgp is not None:
+                dx = self._lgp_block_bwd(P, G, e, dx, B, N, st)
+                continue
             # MLP: x2 = x1 + fc2(gelu(fc1(ln2)))
-            w2_, w2t = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
-            dhpre = self.linear_dgrad(dx, w2_, w2t, act=2, preact=e["hpre"])
-            self.linear_wgrad(dx, e["h"], G[p + ".mlp.fc2.weight"], G[p + ".mlp.fc2.bias"])
-            w1_, w1t = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
-            dln2 = self.linear_dgrad(dhpre, w1_, w1t)
-            self.linear_wgrad(dhpre, e["ln2"], G[p + ".mlp.fc1.weight"], G[p + ".mlp.fc1.bias"])
-            del dhpre
-            dx1 = self.ln_bwd(dln2, e["x1"], e["m2"], e["r2"], P[p + ".norm2.weight"], dx, G[p + ".norm2.weight"],
-                              G[p + ".norm2.bias"])
+            dx1 = self._mlp_bwd(P, G, e, dx)
             # attention: x1 = x0 + proj(attn(ln1))
             wp, wpt = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             dO = self.linear_dgrad(dx1, wp, wpt)
             self.linear_wgrad(dx1, e["O"], G[p + ".attn.proj.weight"], G[p + ".attn.proj.bias"])
-            qkv, Pm = e["qkv"], e["P"]
+            qkv = e["qkv"]
             dqkv = self._empty(M, 3 * D)
             if e.get("geo") is not None:
                 self._relpos_attention_bwd(P, G, e, dO, dqkv, B, N, D, h, hd, scale, st)
-            elif Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
-                delta = self._empty(B * h, N, dtype=torch.float32)
-                check(lib.htrvt_attn_bwd(ptr(qkv), None, ptr(e["O"]), ptr(dO), ptr(e["lse"]), ptr(delta), ptr(dqkv), None,
-                                         B, N, h, hd, scale, self.dti, st), "attn_bwd")
             else:
-                self._attention_bwd_unfused(qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st)
+                self._attention_bwd(qkv, e["P"], e["lse"], e["O"], dO, dqkv, B, N, D, h, hd, scale, st)
             wq, wqt = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             dln1 = self.linear_dgrad(dqkv, wq, wqt)
             self.linear_wgrad(dqkv, e["ln1"], G[p + ".attn.qkv.weight"], G[p + ".attn.qkv.bias"])

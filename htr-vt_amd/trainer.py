@@ -173,6 +173,8 @@ class Trainer:
         batches).  Call after at least one eager step() of the same batch shape (lazily sized workspaces, one-time
         kernel attributes and the engine's streams exist then).  Returns a GraphedStep; its step() has step()'s
         signature and results (bit-identical: same kernels, same order, same scalars)."""
+        if getattr(self.engine.s, "lgp", None) is not None:
+            raise NotImplementedError("Trainer.capture_step is not served for the LGP model: use step()")
         return GraphedStep(self, img, max_target_len, masked, single_stream)
 
     def sam_first_step(self, rho=0.05):

@@ -11,6 +11,9 @@
 * model_sgm_* (/root/reference/model_sgm_2/model/sgm_head.py:118-127): the SGM head's single-head cross-attention
   softmax(Q K^T / sqrt(D)) K with K = V = the (normalised) visual tokens: batched htrvt_gemm + htrvt_softmax_rows over
   [B, L, D] queries and [B, N, D] tokens, forward and backward.
+* model_lgp (/root/reference/model_lgp/model/plg.py): the three operators of its local-global block that no kernel of
+  the hot path covers (csrc/lgp.hip): attention in windows of 12 tokens whose padding slots are rows equal to the qkv
+  bias, average pooling + LayerNorm without affine, linear up-sampling times sigmoid(logit_alpha).
 
 The index bookkeeping (which table entry each (query, key) pair uses) is host glue on tensors of heads * N^2 elements;
 all arithmetic over activations runs in the HIP kernels."""
@@ -290,3 +293,126 @@ def cross_attention(Q, KV):
     if not (Q.is_cuda and KV.is_cuda):
         raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
     return _CrossAttention.apply(Q, KV)
+
+
+# ---- model_lgp (model_lgp/model/plg.py): the three operators of LocalGlobalParallelBlockSimple, csrc/lgp.hip ------------
+
+class _LocalWindowAttention(torch.autograd.Function):
+    """qkv [B*N, 3*heads*hd] + the qkv Linear's float32 bias [3*heads*hd] -> out [B*N, heads*hd]: WindowMHSA1D between its
+    Linear layers.  The bias is an input because the reference's zero padding tokens of a ragged last window become rows
+    equal to it, which real queries attend to; its k / v thirds get the gradient of those rows."""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, B, N, heads, window):
+        D = qkv.shape[1] // 3
+        hd = D // heads
+        dti = dt(qkv.dtype)
+        if qkv_bias.dtype != torch.float32:
+            raise TypeError(f"qkv bias: float32 expected (the parameter as stored), got {qkv_bias.dtype}")
+        qkv, qkv_bias = qkv.contiguous(), qkv_bias.contiguous()
+        out = torch.empty(B * N, D, dtype=qkv.dtype, device=qkv.device)
+        check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(qkv_bias), ptr(out), B, N, heads, hd, window, hd ** -0.5, dti, stream()),
+              "attn_local_fwd")
+        ctx.save_for_backward(qkv, qkv_bias)
+        ctx.dims = (B, N, heads, hd, window, dti)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, N, heads, hd, window, dti = ctx.dims
+        qkv, qkv_bias = ctx.saved_tensors
+        D = heads * hd
+        dout = dout.contiguous().to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        dpad = torch.empty(B, 2 * D, dtype=torch.float32, device=qkv.device)
+        check(lib.htrvt_attn_local_bwd(ptr(qkv), ptr(qkv_bias), ptr(dout), ptr(dqkv), ptr(dpad), B, N, heads, hd, window,
+                                       hd ** -0.5, dti, stream()), "attn_local_bwd")
+        dbias = None
+        if ctx.needs_input_grad[1]:
+            dbias = torch.zeros_like(qkv_bias)
+            if N % window:
+                colsum(dpad, B, 2 * D, 2 * D, dbias.data_ptr() + 4 * D, dti=dt(torch.float32))
+        return dqkv, dbias, None, None, None, None
+
+
+def local_attention_supported(head_dim, window, dtype):
+    return bool(lib.htrvt_attn_local_supported(head_dim, window, dt(dtype)))
+
+
+def local_window_attention(qkv, qkv_bias, B, N, heads, window):
+    """WindowMHSA1D of the LGP fork on its qkv Linear's output: attention inside non-overlapping windows of `window` tokens,
+    the padding slots of a ragged last window being rows equal to `qkv_bias` (not masked).  Differentiable in both."""
+    if not (qkv.is_cuda and qkv_bias.is_cuda):
+        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    if not local_attention_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype):
+        raise ValueError(f"window attention: {lib.htrvt_last_error().decode()}")
+    return _LocalWindowAttention.apply(qkv, qkv_bias, B, N, heads, window)
+
+
+class _PoolNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, B, N, G, eps):
+        D = x.shape[1]
+        dti = dt(x.dtype)
+        x = x.contiguous()
+        z = torch.empty(B * G, D, dtype=x.dtype, device=x.device)
+        mean = torch.empty(B * G, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        check(lib.htrvt_lgp_pool_norm_fwd(ptr(x), ptr(z), ptr(mean), ptr(rstd), B, N, G, D, eps, dti, stream()), "lgp_pool_norm_fwd")
+        ctx.save_for_backward(z, rstd)
+        ctx.dims = (B, N, G, D, dti)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        B, N, G, D, dti = ctx.dims
+        z, rstd = ctx.saved_tensors
+        dz = dz.contiguous().to(z.dtype)
+        dx = torch.empty(B * N, D, dtype=z.dtype, device=z.device)
+        ws = torch.empty(2 * B * G, dtype=torch.float32, device=z.device)
+        check(lib.htrvt_lgp_pool_norm_bwd(ptr(dz), ptr(z), ptr(rstd), ptr(ws), ptr(dx), B, N, G, D, 0, dti, stream()),
+              "lgp_pool_norm_bwd")
+        return dx, None, None, None, None
+
+
+def pool_norm(x, B, N, G, eps=1e-5):
+    """PooledGlobalMHSA up to its qkv: adaptive average pooling of x [B*N, D] to G tokens per image, then LayerNorm without
+    affine -> [B*G, D]"""
+    if not x.is_cuda:
+        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    return _PoolNorm.apply(x, B, N, G, eps)
+
+
+class _UpsampleScale(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, logit_alpha, B, G, N):
+        D = y.shape[1]
+        dti = dt(y.dtype)
+        if logit_alpha.dtype != torch.float32:
+            raise TypeError(f"logit_alpha: float32 expected (the parameter as stored), got {logit_alpha.dtype}")
+        y = y.contiguous()
+        out = torch.empty(B * N, D, dtype=y.dtype, device=y.device)
+        check(lib.htrvt_lgp_upsample_fwd(ptr(y), ptr(logit_alpha), ptr(out), D, B, N, G, D, dti, stream()), "lgp_upsample_fwd")
+        ctx.save_for_backward(y, logit_alpha)
+        ctx.dims = (B, N, G, D, dti)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, N, G, D, dti = ctx.dims
+        y, logit_alpha = ctx.saved_tensors
+        dout = dout.contiguous().to(y.dtype)
+        dy = torch.empty_like(y)
+        dalpha = torch.zeros_like(logit_alpha)
+        ws = torch.empty(lib.htrvt_lgp_upsample_bwd_workspace_floats(B, G), dtype=torch.float32, device=y.device)
+        check(lib.htrvt_lgp_upsample_bwd(ptr(dout), D, ptr(y), ptr(logit_alpha), ptr(dy), ptr(dalpha), ptr(ws), B, N, G, D, dti,
+                                         stream()), "lgp_upsample_bwd")
+        return dy, dalpha, None, None, None
+
+
+def upsample_scale(y, logit_alpha, B, G, N):
+    """the tail of PooledGlobalMHSA: linear interpolation of y [B*G, D] back to N tokens per image (align_corners=False)
+    times sigmoid(logit_alpha), logit_alpha a 0-dim float32 device tensor -> [B*N, D]"""
+    if not (y.is_cuda and logit_alpha.is_cuda):
+        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    return _UpsampleScale.apply(y, logit_alpha, B, G, N)

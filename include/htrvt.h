@@ -451,6 +451,41 @@ int htrvt_sgm_xent_bwd(const float* logits, int ldv, int V, int B, int L, const 
                        void* dlogits, int dtype, void* stream);
 int htrvt_sgm_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, int accumulate, void* stream);
 
+/* ---- the LGP fork's block operators (csrc/lgp.hip; model_lgp/model/plg.py) -------------------------------------------------
+ * float32 and bfloat16, no float atomics (bitwise reproducible), nothing allocated, scalars read from device memory.
+ * Activation and gradient tensors are accessed as 16-byte vectors: their base pointers (an offset one included, e.g. the
+ * right half of a [B N][2D] buffer) must be 16-byte aligned and are refused otherwise.
+ * htrvt_attn_local_*: WindowMHSA1D between its two Linear layers: softmax(q k^T scale) v inside non-overlapping windows of
+ *   `window` tokens (1 ... 16), qkv [B N][3][heads][hd] as the qkv GEMM leaves it, out [B N][heads][hd], hd 64 or 128.  A
+ *   window slot at token index >= N (N % window != 0: the last window of every image) is the row the Linear makes of the
+ *   reference's zero padding token, k = v = qkv_bias (float32 [3 heads hd], its k and v thirds, rounded to dtype): real
+ *   queries attend to it, it is NOT masked.  Nothing is saved for the backward, which recomputes the window's softmax.
+ *   _bwd: dqkv [B N][3][heads][hd] written whole; dpad float32 [B][2][heads hd] overwritten with the summed gradient of each
+ *   image's padding rows' k and v (zeros when N % window == 0) -- a column sum over B adds it to d qkv.bias[D : 3D].
+ *   _supported: 1 if (hd, window, dtype) is served, else 0 with the reason in htrvt_last_error().
+ * htrvt_lgp_pool_norm_fwd: z [B G][D] = LayerNorm without affine (eps) of adaptive_avg_pool1d(x [B N][D]) along the tokens,
+ *   bin g = tokens [floor(g N / G), ceil((g + 1) N / G)); mean / rstd float32 [B G].  1 <= G <= N, D <= 2048.
+ *   _bwd: dx [B N][D] = (accumulate: +=) the gradient of x for dz, each token gathering from the bins that contain it;
+ *   workspace 2 B G floats.
+ * htrvt_lgp_upsample_fwd: out[b][t][0:D] (row stride ldo elements) = sigmoid(logit_alpha[0]) * linear interpolation of
+ *   y [B G][D] to N tokens, F.interpolate(mode="linear", align_corners=False).
+ *   _bwd: dy [B G][D] overwritten by gather from dout (row stride ldd); dlogit_alpha[0] += its gradient by a two-stage
+ *   ordered sum over htrvt_lgp_upsample_bwd_workspace_floats(B, G) floats of workspace. */
+int htrvt_attn_local_supported(int hd, int window, int dtype);
+int htrvt_attn_local_fwd(const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd, int window,
+                         float scale, int dtype, void* stream);
+int htrvt_attn_local_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B, int N,
+                         int heads, int hd, int window, float scale, int dtype, void* stream);
+int htrvt_lgp_pool_norm_fwd(const void* x, void* z, float* mean, float* rstd, int B, int N, int G, int D, float eps, int dtype,
+                            void* stream);
+int htrvt_lgp_pool_norm_bwd(const void* dz, const void* z, const float* rstd, float* workspace, void* dx, int B, int N, int G,
+                            int D, int accumulate, int dtype, void* stream);
+int htrvt_lgp_upsample_fwd(const void* y, const float* logit_alpha, void* out, int64_t ldo, int B, int N, int G, int D,
+                           int dtype, void* stream);
+int64_t htrvt_lgp_upsample_bwd_workspace_floats(int B, int G);
+int htrvt_lgp_upsample_bwd(const void* dout, int64_t ldd, const void* y, const float* logit_alpha, void* dy,
+                           float* dlogit_alpha, float* workspace, int B, int N, int G, int D, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
