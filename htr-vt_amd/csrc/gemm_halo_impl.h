@@ -196,10 +196,13 @@ __device__ __forceinline__ void gemm_halo_s2_body(const P& p, const int block_x)
   const int bimg = rowq / p.Hq, hq = rowq - bimg * p.Hq;
   const int wq0 = seg << 8;
   const int Hh = p.Ho, Ww = p.Wo, Cs = p.Co;                // gathered tensor dY [B, Ho, Wo, Co]: Ho = Hq, Wo = Wq
-  // kernel rows / columns of this class, 2 bits per entry (wave-uniform scalars)
-  const int nrow = ca ? 2 : 1;
-  const int dyp = ca ? (0 | (2 << 2)) : 1;                  // kernel row of row slot r
-  const int dhp = ca ? (1 | (0 << 2)) : 0;                  // dY row = hq + dh
+  // kernel rows / columns of this class, 2 bits per entry (wave-uniform scalars).  Row parity 1 in the LAST coarse row: kernel
+  // row 0 would read dY row Hq, i.e. the padding (NC groups of exact +0 terms, the first ones of the tile) -- such a tile has
+  // the single row slot (kernel row 2 <- dY row hq); everything below, in both roles, derives from nrow / dyp / dhp
+  const bool two = ca && hq + 1 < Hh;
+  const int nrow = two ? 2 : 1;
+  const int dyp = two ? (0 | (2 << 2)) : (ca ? 2 : 1);      // kernel row of row slot r
+  const int dhp = two ? (1 | (0 << 2)) : 0;                  // dY row = hq + dh
   const int ncol = sw == 1 ? 3 : (cb ? 2 : 1);
   const int dxp = sw == 1 ? (0 | (1 << 2) | (2 << 4)) : (cb ? (0 | (2 << 2)) : 1);   // kernel column of column slot j
   const int shp = sw == 1 ? (2 | (1 << 2) | (0 << 4)) : (cb ? (2 | (1 << 2)) : 1);   // halo row shift of column slot j
@@ -436,7 +439,11 @@ __device__ __forceinline__ void gemm_halo_fs2_body(const P& p, const int block_x
   const int rowo = m0 / p.Wo, wo0 = m0 - rowo * p.Wo;     // output row (b * Ho + ho), first output column of this tile
   const int bimg = rowo / p.Ho, ho = rowo - bimg * p.Ho;
   const int NC = p.Cpad / BK;
-  const int NU = 3 * NC;                                  // units = (kernel row, chunk); k-tiles = 3 NU
+  // kernel rows that read the image, [ulo, uhi] (always holds 1), as in gemm_halo_body: a row in the padding would be NC units
+  // of exact +0 terms; both roles walk the same (uhi - ulo + 1) * NC units
+  const int ulo = __builtin_amdgcn_readfirstlane((unsigned)(ho * p.sh - 1) < (unsigned)p.Hi ? 0 : 1);
+  const int uhi = __builtin_amdgcn_readfirstlane((unsigned)(ho * p.sh + 1) < (unsigned)p.Hi ? 2 : 1);
+  const int NU = (uhi - ulo + 1) * NC;                    // units = (kernel row, chunk); k-tiles = 3 NU
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -505,13 +512,13 @@ __device__ __forceinline__ void gemm_halo_fs2_body(const P& p, const int block_x
     auto issueB = [&](int bst, int udy, int ucc, int dx, bool uvalid) {
       lb.template issue<true>(p, lds0 + H::B_BASE + bst * H::B_STAGE, uvalid ? (udy * 3 + dx) * p.Cpad + ucc * BK : p.K, p.K, lw);
     };
-    // ---- prologue: odd image of unit 0, B of k-tiles 0 (dx = 0) and 1 (dx = 2) ----
-    issueA(0, 0, 0, true);
-    issueB(0, 0, 0, 0, true);
-    issueB(1, 0, 0, 2, true);
+    // ---- prologue: odd image of unit 0 = (ulo, chunk 0), B of k-tiles 0 (dx = 0) and 1 (dx = 2) ----
+    issueA(0, ulo, 0, true);
+    issueB(0, ulo, 0, 0, true);
+    issueB(1, ulo, 0, 2, true);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B) : "memory");
     __builtin_amdgcn_s_barrier();
-    int udy = 0, ucc = 0;
+    int udy = ulo, ucc = 0;
     for (int u = 0; u < NU; ++u) {
       int ndy = udy, ncc = ucc + 1;
       if (ncc == NC) {
@@ -612,7 +619,14 @@ __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
   const int Hm = DGRAD ? Hh : p.Ho;                     // forward with a row stride: M rows are OUTPUT rows
   const int bimg = rowi / Hm, hrow = rowi - bimg * Hm;
   const int NC = p.Cpad / BK;
-  const int NG = 3 * NC;
+  // Kernel rows that read the image: row gdy of this tile reads source row hh(gdy), the same for all 256 pixels, and a row in
+  // the padding (the top / bottom image row; both at H = 1) would be NC groups of MFMAs over a zero-filled halo tile -- exact
+  // +0 terms.  The valid rows are the contiguous range [glo, ghi], which always holds 1; BOTH roles walk exactly these
+  // (ghi - glo + 1) * NC groups, so their barrier counts agree for every range.
+  const int hh0 = DGRAD ? hrow + 1 : hrow * p.sh - 1, hh2 = DGRAD ? hrow - 1 : hrow * p.sh + 1;   // hh(0), hh(2)
+  const int glo = __builtin_amdgcn_readfirstlane((unsigned)hh0 < (unsigned)Hh ? 0 : 1);
+  const int ghi = __builtin_amdgcn_readfirstlane((unsigned)hh2 < (unsigned)Hh ? 2 : 1);
+  const int NG = (ghi - glo + 1) * NC;
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -673,15 +687,15 @@ __device__ __forceinline__ void gemm_halo_body(const P& p, const int block_x) {
     auto issueB = [&](int bst, int gdy, int gcc, int dx) {
       lb.template issue<true>(p, lds0 + H::B_BASE + bst * H::B_STAGE, (gdy * 3 + dx) * p.Cpad + gcc * BK, p.K, lw);
     };
-    // ---- prologue: halo tile of group 0, B of k-tiles 0 and 1 ----
-    issueA(0, 0, 0, 0);
-    issueA(1, 0, 0, 0);
-    issueB(0, 0, 0, 0);
-    issueB(1, 0, 0, 1);
+    // ---- prologue: halo tile of group 0 = (glo, chunk 0), B of k-tiles 0 and 1 ----
+    issueA(0, 0, glo, 0);
+    issueA(1, 0, glo, 0);
+    issueB(0, glo, 0, 0);
+    issueB(1, glo, 0, 1);
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H::NP_B) : "memory");
     __builtin_amdgcn_s_barrier();
-    int gdy = 0, gcc = 0;
-    for (int g = 0; g < NG - 1; ++g) {       // every group but the last: the schedule of gemm_halo_body
+    int gdy = glo, gcc = 0;                  // the B offsets keep the true kernel row: (gdy * 3 + dx) * Cpad
+    for (int g = 0; g < NG - 1; ++g) {       // every group but the last, (ghi, NC - 1): the schedule of gemm_halo_body
       int ndy = gdy, ncc = gcc + 1;
       if (ncc == NC) {
         ncc = 0;

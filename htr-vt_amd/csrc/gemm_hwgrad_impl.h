@@ -48,6 +48,54 @@ struct HwGeo {
   static __device__ __forceinline__ int xrot(int r) { return CC == 128 ? 4 * (r & 3) : 4 * ((r >> 1) & 1); }
 };
 
+// k-tiles (64 pixels of one output row, Wk pixels per row) of the pixel range [kbeg, kend) whose output row h satisfies
+// live(h); the range starts at column w0 of a row with in-image index h and may begin and end mid-row.  Scalar: one step per
+// image row of the range (a few dozen at the stem's split factors).
+template <class F>
+__device__ __forceinline__ int hw_live_ktiles(int kbeg, int kend, int w0, int h, int Wk, int Ho, F live) {
+  int n = 0;
+  for (int k = kbeg; k < kend;) {
+    const int px = min(Wk - w0, kend - k);      // pixels of this row inside the range
+    if (live(h)) n += (px + BK - 1) / BK;
+    k += px;
+    w0 = 0;
+    h = h + 1 == Ho ? 0 : h + 1;
+  }
+  return n;
+}
+
+// Workgroup order.  With the dead rows skipped the units of kernel row 1 are the LONG ones (at two image rows they run twice the
+// k-tiles of the rows 0 and 2), and a launch of several rounds (layer 3: 7 ranges x 72 tiles = 504 workgroups on 256 CUs) ends with
+// whatever long workgroup was dispatched last: an XCD whose index interval ended in a block of kernel-row-1 tiles finished no
+// earlier than before the skip.  Both mappings below keep the SET of (range, tile) pairs of every XCD exactly as it was -- the
+// interval [P_x, P_x + n_x) of xcd_range_map, or whole ranges z = x (mod 8) -- and only hand them out long first: the tiles
+// id in [T, 2T), T = ntiles / 3, of each range, then the others in their old order.
+__device__ __forceinline__ int hw_long_first_tile(int s, int ntiles) {      // position s of a range's ntiles -> tile id
+  const int T = ntiles / 3;
+  return s < T ? s + T : (s < 2 * T ? s - T : s);
+}
+__device__ __forceinline__ void hw_xcd_range_map_long_first(int b, int total, int ntiles, int& z, int& id) {
+  const int x = b & 7, s = b >> 3;
+  const int q = total >> 3, r = total & 7;
+  const int P = x * q + (x < r ? x : r), n = q + (x < r ? 1 : 0);       // this XCD's linear indices (xcd_range_map)
+  const int T = ntiles / 3;
+  auto nlong = [&](int a) {       // long pairs among the linear indices below a
+    const int za = a / ntiles, m = a - za * ntiles;
+    return za * T + min(max(m - T, 0), T);
+  };
+  const int l0 = nlong(P), nl = nlong(P + n) - l0;
+  if (s < nl) {                   // the (l0 + s)-th long pair of the launch
+    const int k = l0 + s;
+    z = k / T;
+    id = T + (k - z * T);
+  } else {                        // the (P - l0 + s - nl)-th of the others: 2T per range
+    const int k = P - l0 + s - nl;
+    z = k / (2 * T);
+    const int m = k - z * 2 * T;
+    id = m < T ? m : m + T;
+  }
+}
+
 // PAIR (CC = 128 only): the 128-channel X tile is TWO independent 64-channel units (kernel row, 64-channel chunk) side by
 // side -- channels 0-63 of the tile are unit 2 tm, channels 64-127 unit 2 tm + 1, each read from its own image row.  For a
 // padded channel count that is a multiple of 64 but not of 128 (layer 1: 192 = three chunks x three kernel rows = nine
@@ -69,9 +117,10 @@ __device__ __forceinline__ void gemm_hwgrad_body(const P& p, const int block_x) 
   if (p.split_k > 1 && (p.split_k & 7) == 0) {       // all tiles of one pixel range on one XCD (they read the same x / dY rows)
     const int chunk = block_x / (8 * ntiles), r = block_x - chunk * 8 * ntiles;
     z = chunk * 8 + (r & 7);
-    id = r >> 3;
+    id = PAIR ? r >> 3 : hw_long_first_tile(r >> 3, ntiles);       // (paired units straddle kernel rows: old order)
   } else if (p.split_k > 1 && gridDim.z == 1) {
-    xcd_range_map(block_x, (int)gridDim.x, ntiles, z, id);
+    if (PAIR) xcd_range_map(block_x, (int)gridDim.x, ntiles, z, id);
+    else hw_xcd_range_map_long_first(block_x, (int)gridDim.x, ntiles, z, id);
   }
   const int tm = id / p.tiles_n, tile_n = id - tm * p.tiles_n;
   // unit u of this workgroup (PAIR: two, else one): kernel row dyu[u], first channel ciu[u]; a missing second unit reads zeros
@@ -121,12 +170,31 @@ __device__ __forceinline__ void gemm_hwgrad_body(const P& p, const int block_x) 
   static_assert(H::NPX_MAX + H::NPY <= 5, "vmcnt switch");
   const unsigned lds0 = lds_addr_of(smem);
   const int Hh = p.Hi, Ww = p.Wi;
-  // k-tile position of the NEXT tile to issue: flattened pixel kq = (b * H + h) * W + w0, kept as (row = b*H + h, w0)
+  // k-tile position of the NEXT tile to issue: flattened pixel kq = (b * H + h) * W + w0, kept as (row = b*H + h, w0) and h
   int iq_row = kbeg / Ww, iq_w0 = kbeg - iq_row * Ww, iq_k = kbeg;
+  int iq_h = iq_row % p.Ho;
+  // Output rows whose x row lies in the padding for every unit of this workgroup (kernel row 0 at the top image row, kernel row
+  // 2 at the bottom one) contribute exact zeros: their k-tiles are skipped whole -- neither x nor dY is staged, no k-step runs.
+  // The remaining k-tiles keep their order, so each range's sum is the sum it was.  All of this is scalar (workgroup-uniform).
+  auto row_live = [&](int h) {
+    bool live = (unsigned)(h * p.sh + dyu[0] - 1) < (unsigned)Hh;
+    if (PAIR) live = live || (uok[1] && (unsigned)(h * p.sh + dyu[1] - 1) < (unsigned)Hh);
+    return live;
+  };
+  const int nkt = hw_live_ktiles(kbeg, kend, iq_w0, iq_h, Ww, p.Ho, row_live);
+  auto skip_dead_rows = [&]() {      // move the issue position to the next k-tile of a live row (or past the range)
+    while (iq_k < kend && !row_live(iq_h)) {
+      iq_k += Ww - iq_w0;
+      iq_w0 = 0;
+      ++iq_row;
+      iq_h = iq_h + 1 == p.Ho ? 0 : iq_h + 1;
+    }
+  };
+  skip_dead_rows();
   auto issue = [&](int stage) {
     const unsigned sbase = lds0 + stage * H::STAGE;
     // pixel row iq_row = (image, output row ho) of dY; the x row of kernel row dyi is ho * sh + dyi - 1 (sh = 1 or 2, W stride 1)
-    const int bimg = iq_row / p.Ho, hrow = iq_row - bimg * p.Ho;
+    const int bimg = iq_row / p.Ho, hrow = iq_h;
     bool rowok[2];
     unsigned gbase[2];
 #pragma unroll
@@ -160,6 +228,8 @@ __device__ __forceinline__ void gemm_hwgrad_body(const P& p, const int block_x) 
     if (iq_w0 >= Ww) {
       iq_w0 = 0;
       ++iq_row;
+      iq_h = iq_h + 1 == p.Ho ? 0 : iq_h + 1;
+      skip_dead_rows();
     }
   };
 
@@ -171,7 +241,6 @@ __device__ __forceinline__ void gemm_hwgrad_body(const P& p, const int block_x) 
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int nkt = (kend - kbeg + BK - 1) / BK;
   issue(0);
   issue(1);
   wait_one_tile_in_flight();      // tile 0 landed, tile 1 may fly
@@ -310,9 +379,9 @@ __device__ __forceinline__ void gemm_hwgrad16_body(const P& p, const int block_x
   if (p.split_k > 1 && (p.split_k & 7) == 0) {       // all tiles of one pixel range on one XCD (they read the same x / dY rows)
     const int chunk = block_x / (8 * ntiles), r = block_x - chunk * 8 * ntiles;
     z = chunk * 8 + (r & 7);
-    id = r >> 3;
+    id = hw_long_first_tile(r >> 3, ntiles);
   } else if (p.split_k > 1 && gridDim.z == 1) {
-    xcd_range_map(block_x, (int)gridDim.x, ntiles, z, id);
+    hw_xcd_range_map_long_first(block_x, (int)gridDim.x, ntiles, z, id);
   }
   const int tm = id / p.tiles_n, tile_n = id - tm * p.tiles_n;
   const int dyu = tm / NCC, ciu = (tm - dyu * NCC) * CC;
@@ -363,9 +432,22 @@ __device__ __forceinline__ void gemm_hwgrad16_body(const P& p, const int block_x
   const unsigned lds0 = lds_addr_of(smem);
   const int Hh = p.Hi, Ww = p.Wi, Wk = p.Wo;        // a k-tile = 64 pixels of one OUTPUT row (Wo = Wi at SW = 1)
   int iq_row = kbeg / Wk, iq_w0 = kbeg - iq_row * Wk, iq_k = kbeg;
+  int iq_h = iq_row % p.Ho;
+  // k-tiles of output rows whose x row lies in the padding are skipped whole, as in gemm_hwgrad_body
+  auto row_live = [&](int h) { return (unsigned)(h * p.sh + dyu - 1) < (unsigned)Hh; };
+  const int nkt = hw_live_ktiles(kbeg, kend, iq_w0, iq_h, Wk, p.Ho, row_live);
+  auto skip_dead_rows = [&]() {
+    while (iq_k < kend && !row_live(iq_h)) {
+      iq_k += Wk - iq_w0;
+      iq_w0 = 0;
+      ++iq_row;
+      iq_h = iq_h + 1 == p.Ho ? 0 : iq_h + 1;
+    }
+  };
+  skip_dead_rows();
   auto issue = [&](int stage) {
     const unsigned sbase = lds0 + stage * H::STAGE;
-    const int bimg = iq_row / p.Ho, hrow = iq_row - bimg * p.Ho;
+    const int bimg = iq_row / p.Ho, hrow = iq_h;
     const int hh = hrow * p.sh + dyu - 1;
     const bool rowok = iq_k < kend && (unsigned)hh < (unsigned)Hh;
     const int wfirst = SW == 1 ? iq_w0 - 1 : 2 * iq_w0;
@@ -390,6 +472,8 @@ __device__ __forceinline__ void gemm_hwgrad16_body(const P& p, const int block_x
     if (iq_w0 >= Wk) {
       iq_w0 = 0;
       ++iq_row;
+      iq_h = iq_h + 1 == p.Ho ? 0 : iq_h + 1;
+      skip_dead_rows();
     }
   };
 
@@ -399,7 +483,6 @@ __device__ __forceinline__ void gemm_hwgrad16_body(const P& p, const int block_x
 #pragma unroll
     for (int j = 0; j < CT; ++j) acc[i][j] = f32x4w_t{0.f, 0.f, 0.f, 0.f};
 
-  const int nkt = (kend - kbeg + BK - 1) / BK;
   issue(0);
   issue(1);
   // this wave's pieces of tile 0 have landed, tile 1 may fly (per-wave piece count: NPY + 1 or 2 X pieces)
