@@ -409,6 +409,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply2_kernel(const T* __restrict__
 
 // ------------------------------------------------------------------ first max-pool backward (index based) + ReLU mask
 // g[b,hi,wi,c] = (x*scale+shift > 0) * sum_{windows (ho,wo) containing (hi,wi) with idx == position} dpool[b,ho,wo,c]
+// scale == nullptr: backward of the plain max-pool (htrvt_bn_relu_maxpool with scale == NULL), no ReLU mask
 // One thread per (image, column, channel vector) marches down the input rows; a pooled row (gradient + arg-max
 // bytes of the three windows around this column) is loaded once and serves the three input rows it covers.
 template <typename T>
@@ -429,8 +430,8 @@ __global__ __launch_bounds__(NT) void maxpool_bwd_kernel(const T* __restrict__ d
   float sc[CH], sf[CH];
 #pragma unroll
   for (int j = 0; j < CH; ++j) {
-    sc[j] = scale[cv * CH + j];
-    sf[j] = shift[cv * CH + j];
+    sc[j] = scale ? scale[cv * CH + j] : 1.f;
+    sf[j] = scale ? shift[cv * CH + j] : 0.f;
   }
   const Raw* db = reinterpret_cast<const Raw*>(dpool) + (long long)b * Ho * W * cvec + cv;
   const unsigned char* ib = idx + ((long long)b * Ho * W * cvec + cv) * CH;
@@ -473,7 +474,7 @@ __global__ __launch_bounds__(NT) void maxpool_bwd_kernel(const T* __restrict__ d
     Vec16<T> vx, o;
     vx.raw = xb[(long long)hi * W * cvec];
 #pragma unroll
-    for (int j = 0; j < CH; ++j) o.set(j, fmaf(vx.get(j), sc[j], sf[j]) > 0.f ? acc[j] : 0.f);
+    for (int j = 0; j < CH; ++j) o.set(j, (scale == nullptr || fmaf(vx.get(j), sc[j], sf[j]) > 0.f) ? acc[j] : 0.f);
     gb[(long long)hi * W * cvec] = o.raw;
   };
 
@@ -934,6 +935,7 @@ extern "C" int htrvt_maxpool_bwd(const void* dpool, const uint8_t* idx, const vo
                                  const float* shift, void* g, int B, int H, int W, int C, int dtype, void* stream) {
   const int ch = dtype == HTRVT_BF16 ? 8 : 4;
   HTRVT_REQUIRE(C % ch == 0, "htrvt_maxpool_bwd: C=%d unsupported", C);
+  HTRVT_REQUIRE(dpool && idx && x && g && (scale == nullptr || shift != nullptr), "htrvt_maxpool_bwd: null argument");
   HTRVT_REQUIRE((long long)B * W * (C / ch) < (1ll << 31), "htrvt_maxpool_bwd: too many columns");
   dim3 grid((unsigned)(((long long)B * W * (C / ch) + NT - 1) / NT));
   DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, grid, dim3(NT), 0, (hipStream_t)stream, (const T*)dpool, idx,

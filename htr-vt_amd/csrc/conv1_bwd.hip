@@ -243,6 +243,7 @@ extern "C" int htrvt_conv1_bwd(const void* img, const float* stats, const void* 
   const int ld = htrvt_conv1_bwd_row_floats(C);
   const size_t smem = (size_t)(7 * (W + 4) + 8 * NIMG) * sizeof(float);
   HTRVT_REQUIRE(smem <= 160 * 1024, "conv1_bwd: W=%d does not fit LDS", W);
+  HTRVT_REQUIRE((size_t)ld * sizeof(double) <= 64 * 1024, "conv1_bwd: C=%d too wide for the finalize kernel's LDS", C);
   const int nrows = B * Hp;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == HTRVT_BF16) {
@@ -258,7 +259,6 @@ extern "C" int htrvt_conv1_bwd(const void* img, const float* stats, const void* 
   }
   float* red = partial + (long long)nrows * ld;
   conv1_bwd_reduce_kernel<<<dim3((ld + 63) / 64, S_ROWS), 256, 0, st>>>(partial, red, nrows, ld);
-  HTRVT_REQUIRE((size_t)ld * sizeof(double) <= 64 * 1024, "conv1_bwd: C=%d too wide for the finalize kernel's LDS", C);
   conv1_bwd_finalize_kernel<<<1, 512, (size_t)ld * sizeof(double), st>>>(red, S_ROWS, ld, C, (double)B * Hc * W, w, gamma, mean, rstd, dw,
                                                                         dgamma, dbeta);
   return check_launch("conv1_bwd");

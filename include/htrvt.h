@@ -155,7 +155,10 @@ int htrvt_stem_fwd(const void* img, const float* stats, const float* w, const fl
                    uint8_t* idx, int B, int H, int W, int C, int dtype, int img_u8, void* stream);
 /* BN statistics from partial sums: train mode.  partial [rows][2][C]; count = #elements per channel.
  * Writes scale = gamma*rstd, shift = beta - mean*scale, saves mean/rstd, updates running stats
- * (momentum, unbiased running_var) when running_mean != NULL and adds 1 to *num_batches_tracked (int64, may be NULL). */
+ * (momentum, unbiased running_var) when running_mean != NULL and adds 1 to *num_batches_tracked (int64, may be NULL).
+ * count == 1 has no unbiased variance (torch yields NaN there): running_var then takes the biased one (0).
+ * rows > 256: the rows are first reduced to 64, into scratch the CALLER provides directly behind the partial rows --
+ * `partial` must then be at least (rows + 64) * 2 * C floats; the 64 extra rows are overwritten. */
 int htrvt_bn_finalize(const float* partial, int rows, int C, float count, const float* gamma, const float* beta,
                       float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
                       float* scale, float* shift, float* save_mean, float* save_rstd, void* stream);
@@ -250,7 +253,9 @@ int htrvt_bn_bwd_apply(const void* dy, const void* yact, const void* x, const fl
  * resnet18.py:33-37: dx1 = BN1-backward(g, x1), dx2 = BN2-backward(g, x2) with one read of g */
 int htrvt_bn_bwd_apply2(const void* g, const void* x1, const float* coef1, void* dx1, const void* x2, const float* coef2,
                         void* dx2, int64_t npix, int C, int dtype, void* stream);
-/* backward of htrvt_bn_relu_maxpool: g = d(bn output, ReLU-masked), x = raw conv output [B,H,W,C] */
+/* backward of htrvt_bn_relu_maxpool: g = d(bn output, ReLU-masked), x = raw conv output [B,H,W,C]: dpool scattered through
+ * the arg-max bytes (a byte outside 0..8, e.g. 15, passes nothing), then zeroed where x*scale+shift <= 0.
+ * scale == NULL (shift ignored): backward of the plain max-pool, no mask. */
 int htrvt_maxpool_bwd(const void* dpool, const uint8_t* idx, const void* x, const float* scale, const float* shift,
                       void* g, int B, int H, int W, int C, int dtype, void* stream);
 /* backward of htrvt_pool_tokens w.r.t. x (masked tokens pass no gradient) */
@@ -266,7 +271,9 @@ int htrvt_conv1_wgrad(const void* img, const float* stats, const void* dy, float
  * the arg-max bytes written by htrvt_bn_relu_maxpool (Cin = 1: the chain rule reduces to per-channel sums, see
  * csrc/conv1_bwd.hip).  img [B,H,W] float32, stats = htrvt_img_stats output, w = conv1.weight, mean/rstd = the batch
  * statistics saved by htrvt_bn_finalize.  partial: float32 scratch of htrvt_conv1_bwd_rows(B,H) rows x
- * htrvt_conv1_bwd_row_floats(C) floats.  dw, dgamma, dbeta accumulate. */
+ * htrvt_conv1_bwd_row_floats(C) floats.  dw, dgamma, dbeta accumulate.  Every shape limit (C / 16-byte vector / pick of
+ * channel lanes <= 8 waves, the LDS of the image rows and of the finalize kernel) is checked before the first launch: a
+ * refused call enqueues nothing. */
 int htrvt_conv1_bwd_rows(int B, int H);
 int htrvt_conv1_bwd_row_floats(int C);
 int htrvt_conv1_bwd(const void* img, const float* stats, const void* dpool, const uint8_t* idx, const float* w,
