@@ -1,6 +1,5 @@
-// attention_common.h -- tile staging, LDS fragment reads and small helpers shared by the fused attention kernels
-// (attention.hip: plain / dense-bias scores; attn_relpos.hip: relative-position table).  See attention.hip for the
-// CDNA4 mapping these serve.
+// attention_common.h -- tile staging, LDS fragment reads and small helpers of the fused attention kernels
+// (attention_impl.h, which describes the CDNA4 mapping these serve).
 #pragma once
 
 #include <type_traits>
@@ -152,16 +151,6 @@ __device__ __forceinline__ void store_lane_rows(const f32x16_t (&acc)[ND], bf16_
       v.y = pack_bf16x2(acc[d][4 * g + 2] * mul, acc[d][4 * g + 3] * mul);
       *reinterpret_cast<uint2*>(rowptr + 32 * d + 8 * g + 4 * hf) = v;
     }
-}
-
-template <typename K>
-int set_lds(K kern, int smem, const char* what) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if (e != hipSuccess) {
-    set_error("%s: hipFuncSetAttribute(%d B LDS): %s", what, smem, hipGetErrorString(e));
-    return -2;
-  }
-  return 0;
 }
 
 }  // namespace

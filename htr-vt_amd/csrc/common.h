@@ -117,6 +117,23 @@ void set_error(const char* fmt, ...);
 void set_last_kernel(const char* fmt, ...);   // symbol (as rocprofv3 prints it) of the MFMA kernel an entry point launched
 int check_launch(const char* what);
 
+// Let kernel KERN be launched with up to `bytes` of dynamic LDS (more than 64 KB needs the attribute).  It is set once per
+// device: the attribute belongs to the device that is current at the launch.  0, or -2 with the error set.
+template <auto KERN>
+int allow_dynamic_lds(int bytes, const char* what) {
+  static bool done[64] = {};
+  int dev = -1;
+  const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;   // unknown device: set it every time
+  if (known && done[dev]) return 0;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    set_error("%s: hipFuncSetAttribute(%d B LDS): %s", what, bytes, hipGetErrorString(e));
+    return -2;
+  }
+  if (known) done[dev] = true;
+  return 0;
+}
+
 }  // namespace htrvt
 
 #define HTRVT_REQUIRE(cond, ...)        \

@@ -217,17 +217,9 @@ __global__ __launch_bounds__(64 * NWAVE, 3) void conv1x1_fwd_kernel(const KParam
 
 template <int KS, int NWAVE>
 int launch_c1(const KParams& p, int nwg, hipStream_t st) {
-  static bool attr_done = false;
-  auto kern = conv1x1_fwd_kernel<KS, NWAVE>;
+  constexpr auto kern = conv1x1_fwd_kernel<KS, NWAVE>;
   constexpr int smem = C1<KS, NWAVE>::LDS_BYTES;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  if (int rc = allow_dynamic_lds<kern>(smem, "conv1x1_fwd_kernel")) return rc;
   hipLaunchKernelGGL(kern, dim3(nwg * p.tiles_n), dim3(64 * NWAVE), smem, st, p);
   set_last_kernel("conv1x1_fwd_kernel<%d, %d>", KS, NWAVE);
   const int rc = check_launch("conv1x1_fwd_kernel");

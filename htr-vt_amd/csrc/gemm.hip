@@ -352,16 +352,8 @@ __global__ __launch_bounds__(NTHREADS) void splitk_reduce_kernel(const float* __
 template <typename T, int BM, int BN, int AL, int BL, int GATHER>
 int launch(const KParams& p, int zdim, hipStream_t st) {
   constexpr int smem = 2 * (TileGeom<T, BM, AL>::BYTES + TileGeom<T, BN, BL>::BYTES);
-  static bool attr_done = false;
-  auto kern = gemm_kernel<T, BM, BN, AL, BL, GATHER>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_kernel<T, BM, BN, AL, BL, GATHER>;
+  if (int rc = allow_dynamic_lds<kern>(smem, "gemm_kernel")) return rc;
   dim3 grid(p.tiles_m * p.tiles_n, 1, zdim);
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), smem, st, p);
   set_last_kernel("gemm_kernel<%s, %d, %d, %d, %d, %d>", sizeof(T) == 4 ? "float" : "bf16_t", BM, BN, AL, BL, GATHER);

@@ -759,16 +759,8 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const KParams p) {
 template <class C, int GATHER, int EPI>
 int launch(const KParams& p, int zdim, hipStream_t st) {
   static_assert(C::LDS_BYTES <= 160 * 1024, "LDS");
-  static bool attr_done = false;
-  auto kern = gemm8p_kernel<C, GATHER, EPI>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm8p_kernel<C, GATHER, EPI>;
+  if (int rc = allow_dynamic_lds<kern>(C::LDS_BYTES, "gemm8p_kernel")) return rc;
   dim3 grid(p.tiles_m * p.tiles_n, 1, zdim);
   hipLaunchKernelGGL(kern, grid, dim3(512), C::LDS_BYTES, st, p);
   set_last_kernel("gemm8p_kernel<Cfg<%d, %d, %d>, %d, %d>", C::BN, C::WARPS_M, C::WARPS_N, GATHER, EPI);

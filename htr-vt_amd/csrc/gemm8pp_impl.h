@@ -544,16 +544,8 @@ __global__ __launch_bounds__(512) void gemm8pp_kernel(const KParams p) {
 template <class C, int EPI>
 int launch_persistent(const KParams& p, int nwg, hipStream_t st) {
   static_assert(PCfg<C>::LDS_BYTES <= 160 * 1024, "LDS");
-  static bool attr_done = false;
-  auto kern = gemm8pp_kernel<C, EPI>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PCfg<C>::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", PCfg<C>::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm8pp_kernel<C, EPI>;
+  if (int rc = allow_dynamic_lds<kern>(PCfg<C>::LDS_BYTES, "gemm8pp_kernel")) return rc;
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), PCfg<C>::LDS_BYTES, st, p);
   set_last_kernel("gemm8pp_kernel<Cfg<%d, %d, %d>, %d>", C::BN, C::WARPS_M, C::WARPS_N, EPI);
   const int rc = check_launch("gemm8pp_kernel");

@@ -255,15 +255,7 @@ __global__ __launch_bounds__(512) void gemm8pt_kernel(const KParams p) {
 
 inline int launch_t(const KParams& p, int zdim, hipStream_t st) {
   using C = Cfg<256, 2, 4>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8pt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  if (int rc = allow_dynamic_lds<gemm8pt_kernel>(C::LDS_BYTES, "gemm8pt_kernel")) return rc;
   hipLaunchKernelGGL(gemm8pt_kernel, dim3(p.tiles_m * p.tiles_n, 1, zdim), dim3(512), C::LDS_BYTES, st, p);
   set_last_kernel("gemm8pt_kernel");
   const int rc = check_launch("gemm8pt_kernel");

@@ -1032,16 +1032,8 @@ int launch(const KParams& p, int zdim, hipStream_t st) {
   constexpr int NTH = BM * 2 + SPEC * 256;
   constexpr int smem = NSTAGE == 5 ? 3 * Geo<BM>::BYTES + 2 * Geo<BN>::BYTES : NSTAGE * (Geo<BM>::BYTES + Geo<BN>::BYTES);
   static_assert(smem <= 160 * 1024, "LDS");
-  static bool attr_done = false;
-  auto kern = gemm_dma_kernel<BM, BN, AL, BL, GATHER, SPEC, NSTAGE>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", smem, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_dma_kernel<BM, BN, AL, BL, GATHER, SPEC, NSTAGE>;
+  if (int rc = allow_dynamic_lds<kern>(smem, "gemm_dma_kernel")) return rc;
   dim3 grid(p.tiles_m * p.tiles_n, 1, zdim);
   if (p.split_k > 1) grid = dim3(p.split_k * p.tiles_m * p.tiles_n, 1, 1);   // XCD-grouped K ranges
   hipLaunchKernelGGL(kern, grid, dim3(NTH), smem, st, p);

@@ -382,16 +382,8 @@ __global__ __launch_bounds__(768) void gemm_halo_s2_kernel(const KParams p) {
 template <int BN>
 int launch_halo_s2(const KParams& p, hipStream_t st) {
   constexpr int LDS = HaloGeo<BN>::LDS_BYTES;
-  static bool attr_done = false;
-  auto kern = gemm_halo_s2_kernel<BN>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_halo_s2_kernel<BN>;
+  if (int rc = allow_dynamic_lds<kern>(LDS, "gemm_halo_s2_kernel")) return rc;
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(768), LDS, st, p);
   set_last_kernel("gemm_halo_s2_kernel<%d>", BN);
   const int rc = check_launch("gemm_halo_s2_kernel");
@@ -576,16 +568,8 @@ __global__ __launch_bounds__(768) void gemm_halo_fs2_kernel(const KParams p) {
 template <int BN, bool F32 = false>
 int launch_halo_fs2(const KParams& p, hipStream_t st) {
   constexpr int LDS = HaloFs2Geo<BN>::LDS_BYTES;
-  static bool attr_done = false;
-  auto kern = gemm_halo_fs2_kernel<BN, F32>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_halo_fs2_kernel<BN, F32>;
+  if (int rc = allow_dynamic_lds<kern>(LDS, "gemm_halo_fs2_kernel")) return rc;
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(768), LDS, st, p);
   if (F32) set_last_kernel("gemm_halo_fs2_kernel<%d, f32>", BN);
   else set_last_kernel("gemm_halo_fs2_kernel<%d>", BN);
@@ -755,16 +739,8 @@ __global__ __launch_bounds__(768) void gemm_halo_kernel(const KParams p) {
 template <int BN, bool DGRAD, bool F32 = false>
 int launch_halo(const KParams& p, hipStream_t st) {
   using H = HaloGeo<BN>;
-  static bool attr_done = false;
-  auto kern = gemm_halo_kernel<BN, DGRAD, F32>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, H::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", H::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_halo_kernel<BN, DGRAD, F32>;
+  if (int rc = allow_dynamic_lds<kern>(H::LDS_BYTES, "gemm_halo_kernel")) return rc;
   hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(768), H::LDS_BYTES, st, p);
   if (F32) set_last_kernel("gemm_halo_kernel<%d, %s, f32>", BN, DGRAD ? "true" : "false");
   else set_last_kernel("gemm_halo_kernel<%d, %s>", BN, DGRAD ? "true" : "false");

@@ -611,16 +611,8 @@ __global__ __launch_bounds__(768) void gemm_hwgrad16_kernel(const KParams p) {
 template <int CC, int BN, int SW = 1>
 int launch_hwgrad16(const KParams& p, int zdim, hipStream_t st) {
   using H = Hw16Geo<CC, BN, SW>;
-  static bool attr_done = false;
-  auto kern = gemm_hwgrad16_kernel<CC, BN, SW>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, H::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", H::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_hwgrad16_kernel<CC, BN, SW>;
+  if (int rc = allow_dynamic_lds<kern>(H::LDS_BYTES, "gemm_hwgrad16_kernel")) return rc;
   const int ntiles = 3 * (p.Cpad / CC) * p.tiles_n;
   dim3 grid(ntiles, 1, zdim);
   if (p.split_k > 1) grid = dim3(p.split_k * ntiles, 1, 1);
@@ -642,16 +634,8 @@ __global__ __launch_bounds__(768) void gemm_hwgrad_kernel(const KParams p) {
 template <int CC, int BN, bool PAIR = false>
 int launch_hwgrad(const KParams& p, int zdim, hipStream_t st) {
   using H = HwGeo<CC, BN>;
-  static bool attr_done = false;
-  auto kern = gemm_hwgrad_kernel<CC, BN, PAIR>;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, H::LDS_BYTES);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%d B LDS): %s", H::LDS_BYTES, hipGetErrorString(e));
-      return -2;
-    }
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_hwgrad_kernel<CC, BN, PAIR>;
+  if (int rc = allow_dynamic_lds<kern>(H::LDS_BYTES, "gemm_hwgrad_kernel")) return rc;
   const int ntiles = (PAIR ? (3 * (p.Cpad / 64) + 1) / 2 : 3 * (p.Cpad / CC)) * p.tiles_n;
   dim3 grid(ntiles, 1, zdim);
   if (p.split_k > 1) grid = dim3(p.split_k * ntiles, 1, 1);

@@ -191,12 +191,7 @@ int stem_mfma_try_launch(const void* img, const float* stats, const float* w, co
   const int RS = (SM_PIX * nblk + 36 + 7) & ~7;
   const size_t smem = (((size_t)7 * RS * 2 + 15) & ~(size_t)15) + (size_t)(C / 32) * 64 * 16 + (size_t)(SM_NT / 64) * SM_STAGE;
   if (smem > 160 * 1024) return 0;
-  static bool attr_done = false;
-  if (smem > 64 * 1024 && !attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(stem_mfma_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return 0;
-    attr_done = true;
-  }
+  if (smem > 64 * 1024 && allow_dynamic_lds<stem_mfma_fwd_kernel>(160 * 1024, "stem_mfma_fwd")) return 0;
   const int Hc = H / 2, Hp = (Hc - 1) / 2 + 1;
   hipLaunchKernelGGL(stem_mfma_fwd_kernel, dim3(B * Hp), dim3(SM_NT), smem, st, img, stats, w, scale, shift, (bf16_t*)y, idx, H, W,
                      C, img_u8, nblk, RS);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bank-conflict check of the LDS images used by csrc/attention.hip (CPU only, no GPU needed).
+"""Bank-conflict check of the LDS images used by the fused attention kernels, csrc/attention_impl.h (CPU only, no GPU needed).
 
 Applies the gfx950 banking rules of /opt/skills/guides/MI355X_MICROARCH.md (LDS table): ds_read_b128 is served in four
 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, {32-35,44-47,52-59}, {36-43,48-51,60-63}; ds_read_b64 and
@@ -61,7 +61,7 @@ def tr_read(hd, row0, s, dt, second):
 
 
 def lane_forms_ok(hd):
-    """the per-lane XOR forms of csrc/attention.hip (LaneAddr) against off() for every lane and compile-time index"""
+    """the per-lane XOR forms of csrc/attention_common.h (LaneAddr) against off() for every lane and compile-time index"""
     rowb_ = hd * 2
     for lane in range(64):
         h, g, i = lane >> 5, (lane >> 4) & 1, lane & 15
