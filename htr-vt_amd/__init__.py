@@ -14,6 +14,7 @@ from .ctc import ctc_forward_backward, ctc_loss, greedy_decode  # noqa: F401,E40
 from .data import prepare_lines  # noqa: F401,E402
 from .ema import ModelEma  # noqa: F401,E402
 from .engine import Engine, ModelShape  # noqa: F401,E402
+from .valid import error_counts, symbol_tables, validation  # noqa: F401,E402
 
 
 def mark_weights_dirty(model):

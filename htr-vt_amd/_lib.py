@@ -120,6 +120,8 @@ PROTOTYPES = {
     "htrvt_sam_restore": (i32, [vp, vp, i64, vp]),
     "htrvt_ema_update": (i32, [vp, i32, i64, f64, vp]),
     "htrvt_ctc_greedy_decode": (i32, [vp, i32, i32, i32, i64, i32, vp, vp, vp]),
+    "htrvt_error_counts_max_tgt": (i32, []),
+    "htrvt_error_counts": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "htrvt_adamw": (i32, [vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, vp]),
     "htrvt_adamw_scalars": (i32, [f64, f64, f64, f64, f64, i32, vp]),
     "htrvt_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),

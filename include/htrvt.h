@@ -41,7 +41,8 @@ extern "C" {
 int htrvt_version(void);
 const char* htrvt_last_error(void);
 /* symbol of the MFMA kernel the last htrvt_gemm call of this thread launched, spelled as rocprofv3 prints it
- * (e.g. "gemm_dma_kernel<256, 192, 0, 0, 2, 1, 2>"): lets bench.py name its roofline kernel by the profiler's symbol */
+ * (e.g. "gemm_dma_kernel<256, 192, 0, 0, 2, 1, 2>"): lets bench.py name its roofline kernel by the profiler's symbol.
+ * htrvt_error_counts records its kernel here as well; a call that is refused leaves the value alone. */
 const char* htrvt_last_kernel(void);
 
 /* One MFMA GEMM   C[m][n] = alpha * sum_k A(m,k) * B(n,k)  (+ epilogue).
@@ -410,6 +411,23 @@ int htrvt_ema_update(const HtrvtEmaEntry* table, int count, int64_t max_numel, d
  * their log-softmax), out [B,T] int32. */
 int htrvt_ctc_greedy_decode(const float* logits, int B, int T, int C, int64_t ld, int ncharacter, int32_t* out,
                             int32_t* out_len, void* stream);
+/* valid.py:49-75, the metric loop: per sample b the Levenshtein distance (unit insert / delete / substitute costs) between
+ * the decoded prediction and the label, over characters (editdistance.eval(pred, gt), valid.py:50) and over the word lists
+ * utils.format_string_for_wer(s).split(" ") (valid.py:59-63, utils/utils.py:176-179), with the lengths CER and WER divide by.
+ *   counts[b] = { ed_char, len(gt), ed_word, len(gt_words) };  totals[0:4] += their column sums (integer atomics; may be NULL).
+ * pred [B][ld_pred] / pred_len [B] are htrvt_ctc_greedy_decode's out / out_len; tgt / tgt_len / tgt_off are the label arrays
+ * of htrvt_ctc_loss.  Symbols are class indices; two of them are the same character iff canon[] maps them to the same value,
+ * and kind[] says what a character is to the word split: 0 ordinary, 1 separator (space, newline), 2 punctuation (a word of
+ * its own), 3 other white space (ordinary inside a string, dropped at its ends as str.strip does).  An index outside
+ * [0, nsym) reads no table: it stands for itself and is ordinary.  A string without a word is ONE empty word, as "".split(" ")
+ * is.  Words are equal iff their canonical symbols are.  One workgroup per sample, everything in LDS and registers.
+ * Limits: max_pred <= 16384 (the decode's own), ld_pred >= max_pred, max_tgt <= htrvt_error_counts_max_tgt() (512).  A
+ * violation, a null pointer other than totals, B <= 0 or nsym <= 0 returns a negative code before anything is launched.
+ * pred_len[b] / tgt_len[b] live on the device: a value beyond max_pred / max_tgt is read as that maximum. */
+int htrvt_error_counts_max_tgt(void);
+int htrvt_error_counts(const int32_t* pred, int64_t ld_pred, const int32_t* pred_len, const int32_t* tgt, const int32_t* tgt_len,
+                       const int32_t* tgt_off, const int32_t* canon, const uint8_t* kind, int nsym, int B, int max_pred,
+                       int max_tgt, int32_t* counts, int64_t* totals, void* stream);
 
 /* ---- in front of the path: the loader's per-image preparation -------------------------------------
  * data/dataset.py:104-135 for a ragged batch of grey uint8 scans: aspect-preserving resize to height H (npThum: width' =
