@@ -12,11 +12,9 @@ statistics, logits, parameters and parameter gradients are float32.
 """
 from __future__ import annotations
 
-import math
-
 import torch
 
-from . import ops
+from . import ops, seq_ops
 from ._lib import lib, check, RelayoutJob, RELAYOUT_PACK_CONV, RELAYOUT_CAST_TRANSPOSE, RELAYOUT_UNPACK_WGRAD, RELAYOUT_ARG_JOBS
 from .ops import KMAJOR, MNMAJOR, GATHER_CONV_DGRAD, GATHER_CONV_FWD, GATHER_CONV_WGRAD, ConvGeom, cpad, dt, gemm, ptr, stream
 
@@ -873,27 +871,10 @@ class Engine:
 
     # ------------------------------------------------------------------ LayerNorm pieces
     def ln_fwd(self, x, gamma, beta, save):
-        rows, D = x.shape
-        y = torch.empty_like(x)
-        mean = self._empty(rows, dtype=torch.float32) if save else None
-        rstd = self._empty(rows, dtype=torch.float32) if save else None
-        check(lib.htrvt_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), rows, D, self.s.ln_eps, self.dti,
-                                      stream()), "layernorm_fwd")
-        return y, mean, rstd
+        return seq_ops.layernorm_fwd(x, gamma, beta, self.s.ln_eps, save)
 
     def ln_bwd(self, dy, x, mean, rstd, gamma, dres, dgamma, dbeta):
-        rows, D = x.shape
-        nblk = lib.htrvt_layernorm_bwd_blocks(rows)
-        partial = self._empty(nblk, 2, D, dtype=torch.float32)
-        dx = torch.empty_like(x)
-        check(lib.htrvt_layernorm_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx), ptr(partial),
-                                      rows, D, self.dti, stream()), "layernorm_bwd")
-        if dbeta.data_ptr() == dgamma.data_ptr() + 4 * D:   # weight and bias adjacent in the flat gradient buffer: one launch
-            ops.colsum(partial, nblk, 2 * D, 2 * D, dgamma, dti=0)
-        else:
-            ops.colsum(partial, nblk, D, 2 * D, dgamma, dti=0)
-            ops.colsum(partial.data_ptr() + 4 * D, nblk, D, 2 * D, dbeta, dti=0)
-        return dx
+        return seq_ops.layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres)
 
     # ------------------------------------------------------------------ forward
     def forward(self, P, img, keep_mask=None, train=False, save=False, want_features=False):
@@ -1078,26 +1059,23 @@ class Engine:
 
         # --- transformer blocks (HTR_VT.py:80-83, 27-39) ---
         M = B * N
-        h, hd = s.heads, s.hd
-        scale = hd ** -0.5
         xt = tok.view(M, D)
         enc_saved = []
         for i in range(s.depth):
             p = f"blocks.{i}"
             if s.lgp is not None:
-                e, xt = self._lgp_block_fwd(P, p, xt, B, N, save, st)
+                e, xt = self._lgp_block_fwd(P, p, xt, B, N, save)
                 if save:
                     enc_saved.append(e)
                 continue
             ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
             wq, _ = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             qkv = self.linear_fwd(ln1, wq, P[p + ".attn.qkv.bias"])
-            O = self._empty(M, D)
             geo = s.relpos[i] if s.relpos is not None else None
             if geo is not None:
-                Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st)
+                O, Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, B, N, save)
             else:
-                Pm, lse = self._attention_fwd(qkv, O, B, N, D, h, hd, scale, save, st)
+                O, Pm, lse = self._attention_fwd(qkv, B, N, save)
             wp, _ = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             x1 = self.linear_fwd(O, wp, P[p + ".attn.proj.bias"], residual=xt)
             x2, mlp = self._mlp_fwd(P, p, x1, save)
@@ -1126,22 +1104,19 @@ class Engine:
             return y, feats
         return y
 
-    def _attention_fwd(self, qkv, O, B, N, D, h, hd, scale, save, st):
-        """full self-attention over N tokens: (P or None, lse2 or None) as the backward wants them"""
-        if self.fused_attention and lib.htrvt_attn_supported(N, hd, self.dti):
-            # bf16: one launch, scores / probabilities stay on chip; lse2 is what the recomputing backward needs
-            lse = self._empty(B * h, N, dtype=torch.float32) if save else None
-            check(lib.htrvt_attn_fwd(ptr(qkv), None, ptr(O), ptr(lse), B, N, h, hd, scale, self.dti, st), "attn_fwd")
-            return None, lse
-        return self._attention_fwd_unfused(qkv, O, B, N, D, h, hd, scale, st), None
+    def _attention_fwd(self, qkv, B, N, save):
+        """full self-attention over N tokens: (O, P or None, lse or None), P / lse as the backward wants them"""
+        h = self.s.heads
+        if self.fused_attention and lib.htrvt_attn_supported(N, self.s.hd, self.dti):
+            # bf16: one launch, scores / probabilities stay on chip; lse is what the recomputing backward needs
+            O, lse = seq_ops.attention_fwd(qkv, B, N, h, save=save)
+            return O, None, lse
+        return (*seq_ops.attention_unfused_fwd(qkv, B, N, h), None)
 
-    def _attention_bwd(self, qkv, Pm, lse, O, dO, dqkv, B, N, D, h, hd, scale, st):
+    def _attention_bwd(self, qkv, Pm, lse, O, dO, B, N):
         if Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
-            delta = self._empty(B * h, N, dtype=torch.float32)
-            check(lib.htrvt_attn_bwd(ptr(qkv), None, ptr(O), ptr(dO), ptr(lse), ptr(delta), ptr(dqkv), None,
-                                     B, N, h, hd, scale, self.dti, st), "attn_bwd")
-        else:
-            self._attention_bwd_unfused(qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st)
+            return seq_ops.attention_bwd(qkv, O, dO, lse, B, N, self.s.heads)
+        return seq_ops.attention_unfused_bwd(qkv, Pm, dO, B, N, self.s.heads)
 
     def _mlp_fwd(self, P, p, x1, save):
         """x2 = x1 + fc2(gelu(fc1(norm2(x1)))); returns (x2, what the backward keeps)"""
@@ -1167,39 +1142,31 @@ class Engine:
                            G[p + ".norm2.bias"])
 
     # ------------------------------------------------------------------ the LGP fork's block (model_lgp/model/plg.py:172-212)
-    def _lgp_block_fwd(self, P, p, xt, B, N, save, st):
+    def _lgp_block_fwd(self, P, p, xt, B, N, save):
         """x1 = x + fuse([local_attn(y) | global_attn(y)]), y = norm1(x); x2 = x1 + mlp(norm2(x1)).  The two branches write
         the halves of one [B N][2D] buffer (no cat copy); csrc/lgp.hip has the window attention, the pooling + LayerNorm in
         front of the global branch and the scaled up-sampling behind it, everything else is the kernels of the v1 block."""
         s = self.s
-        D, h, hd, M = s.D, s.heads, s.hd, B * N
-        scale = hd ** -0.5
+        D, h, M = s.D, s.heads, B * N
         win, gtok, beps = s.lgp
         Gt = min(gtok, N)
-        es = xt.element_size()
         ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
         cat = self._empty(M, 2 * D)
         # local branch: qkv -> attention inside windows (padding slots = the qkv bias) -> proj into the left half
         lb = P[p + ".local_attn.qkv.bias"]
         wq, _ = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
         qkv = self.linear_fwd(ln1, wq, lb)
-        O = self._empty(M, D)
-        check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(lb), ptr(O), B, N, h, hd, win, scale, self.dti, st), "attn_local_fwd")
+        O = seq_ops.local_attention_fwd(qkv, lb, B, N, h, win)
         wp, _ = self._lin_w(p + ".local_attn.proj", P[p + ".local_attn.proj.weight"])
         gemm(O, wp, cat, dtype=self.dtype, M=M, N=D, K=D, lda=D, ldb=D, ldc=2 * D, bias=P[p + ".local_attn.proj.bias"])
         # global branch: pool to Gt tokens + LayerNorm -> qkv -> full attention -> proj -> up-sample * sigmoid(alpha), right half
-        z = self._empty(B * Gt, D)
-        zmean, zrstd = self._empty(B * Gt, dtype=torch.float32), self._empty(B * Gt, dtype=torch.float32)
-        check(lib.htrvt_lgp_pool_norm_fwd(ptr(ln1), ptr(z), ptr(zmean), ptr(zrstd), B, N, Gt, D, beps, self.dti, st),
-              "lgp_pool_norm_fwd")
+        z, _, zrstd = seq_ops.pool_norm_fwd(ln1, B, N, Gt, beps)
         wgq, _ = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
         qkvg = self.linear_fwd(z, wgq, P[p + ".global_attn.qkv.bias"])
-        Og = self._empty(B * Gt, D)
-        Pg, lseg = self._attention_fwd(qkvg, Og, B, Gt, D, h, hd, scale, save, st)
+        Og, Pg, lseg = self._attention_fwd(qkvg, B, Gt, save)
         wgp, _ = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
         yg = self.linear_fwd(Og, wgp, P[p + ".global_attn.proj.bias"])
-        check(lib.htrvt_lgp_upsample_fwd(ptr(yg), ptr(P[p + ".global_attn.logit_alpha"]), cat.data_ptr() + D * es, 2 * D,
-                                         B, N, Gt, D, self.dti, st), "lgp_upsample_fwd")
+        seq_ops.upsample_fwd(yg, P[p + ".global_attn.logit_alpha"], cat[:, D:], B, N, Gt)
         wf, _ = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
         x1 = self.linear_fwd(cat, wf, P[p + ".fuse.bias"], residual=xt)
         x2, mlp = self._mlp_fwd(P, p, x1, save)
@@ -1209,29 +1176,22 @@ class Engine:
                      Og=Og, yg=yg, x1=x1, Gt=Gt, **mlp)
         return e, x2
 
-    def _lgp_block_bwd(self, P, G, e, dx, B, N, st):
+    def _lgp_block_bwd(self, P, G, e, dx, B, N):
         s = self.s
-        D, h, hd, M = s.D, s.heads, s.hd, B * N
-        scale = hd ** -0.5
+        D, h = s.D, s.heads
         win, Gt = s.lgp[0], e["Gt"]
         p = e["p"]
         dx1 = self._mlp_bwd(P, G, e, dx)
-        es = dx1.element_size()
         wf, wft = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
         dcat = self.linear_dgrad(dx1, wf, wft)                       # [M][2D]: left half d local proj, right half d global
         self.linear_wgrad(dx1, e["cat"], G[p + ".fuse.weight"], G[p + ".fuse.bias"])
         # global branch
-        alpha = P[p + ".global_attn.logit_alpha"]
-        dyg = self._empty(B * Gt, D)
-        ws = self._empty(lib.htrvt_lgp_upsample_bwd_workspace_floats(B, Gt), dtype=torch.float32)
-        check(lib.htrvt_lgp_upsample_bwd(dcat.data_ptr() + D * es, 2 * D, ptr(e["yg"]), ptr(alpha), ptr(dyg),
-                                         ptr(G[p + ".global_attn.logit_alpha"]), ptr(ws), B, N, Gt, D, self.dti, st),
-              "lgp_upsample_bwd")
+        dyg = seq_ops.upsample_bwd(dcat[:, D:], e["yg"], P[p + ".global_attn.logit_alpha"], G[p + ".global_attn.logit_alpha"],
+                                   B, N, Gt)
         wgp, wgpt = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
         dOg = self.linear_dgrad(dyg, wgp, wgpt)
         self.linear_wgrad(dyg, e["Og"], G[p + ".global_attn.proj.weight"], G[p + ".global_attn.proj.bias"])
-        dqkvg = self._empty(B * Gt, 3 * D)
-        self._attention_bwd(e["qkvg"], e["Pg"], e["lseg"], e["Og"], dOg, dqkvg, B, Gt, D, h, hd, scale, st)
+        dqkvg = self._attention_bwd(e["qkvg"], e["Pg"], e["lseg"], e["Og"], dOg, B, Gt)
         wgq, wgqt = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
         dz = self.linear_dgrad(dqkvg, wgq, wgqt)
         self.linear_wgrad(dqkvg, e["z"], G[p + ".global_attn.qkv.weight"], G[p + ".global_attn.qkv.bias"])
@@ -1240,100 +1200,48 @@ class Engine:
         dO = self.linear_dgrad(dcat, wp, wpt, cols=(0, D))
         self.linear_wgrad(dcat, e["O"], G[p + ".local_attn.proj.weight"], G[p + ".local_attn.proj.bias"], cols=(0, D))
         lb, glb = P[p + ".local_attn.qkv.bias"], G[p + ".local_attn.qkv.bias"]
-        dqkv = self._empty(M, 3 * D)
-        dpad = self._empty(B, 2 * D, dtype=torch.float32)
-        check(lib.htrvt_attn_local_bwd(ptr(e["qkv"]), ptr(lb), ptr(dO), ptr(dqkv), ptr(dpad), B, N, h, hd, win, scale, self.dti,
-                                       st), "attn_local_bwd")
+        dqkv, dpad = seq_ops.local_attention_bwd(e["qkv"], lb, dO, B, N, h, win)
         wq, wqt = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
         dln1 = self.linear_dgrad(dqkv, wq, wqt)
         self.linear_wgrad(dqkv, e["ln1"], G[p + ".local_attn.qkv.weight"], glb)
         if N % win:     # the padding rows' k / v gradient; on the weight-gradient stream, behind the bias column sum above
             self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, glb.data_ptr() + 4 * D, dti=0), dpad)
-        ws2 = self._empty(2 * B * Gt, dtype=torch.float32)
-        check(lib.htrvt_lgp_pool_norm_bwd(ptr(dz), ptr(e["z"]), ptr(e["zrstd"]), ptr(ws2), ptr(dln1), B, N, Gt, D, 1, self.dti,
-                                          st), "lgp_pool_norm_bwd")
+        seq_ops.pool_norm_bwd(dz, e["z"], e["zrstd"], B, N, Gt, dx=dln1)      # added to the local branch's gradient
         return self.ln_bwd(dln1, e["x0"], e["m1"], e["r1"], P[p + ".norm1.weight"], dx1, G[p + ".norm1.weight"],
                            G[p + ".norm1.bias"])
 
-    def _relpos_attention_fwd(self, P, p, geo, qkv, O, B, N, D, h, hd, scale, save, st):
+    def _relpos_attention_fwd(self, P, p, geo, qkv, B, N, save):
         """attention of a window-fork block with its relative-position table: bf16 on the table-driven fused kernels
-        (csrc/attn_relpos.hip), float32 through the dense bias (htrvt_relpos_bias_fwd) + the unfused GEMM route"""
+        (csrc/attn_relpos.hip), float32 through the dense bias + the batched-GEMM route; (O, P or None, lse or None)"""
         s = self.s
+        h, tp = s.heads, s.table_patches
         ws, shift = geo
         tab = P[p + ".attn.relative_position_bias_table"]
         if self.dtype == torch.bfloat16:
-            if not lib.htrvt_attn_relpos_supported(N, hd, self.dti, s.table_patches, ws, shift):
+            if not lib.htrvt_attn_relpos_supported(N, s.hd, self.dti, tp, ws, shift):
                 raise RuntimeError(f"{p}: relative-position attention: {lib.htrvt_last_error().decode()}")
-            lse = self._empty(B * h, N, dtype=torch.float32) if save else None
-            check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(tab), ptr(O), ptr(lse), B, N, h, hd, scale, s.table_patches, ws, shift,
-                                            self.dti, st), "attn_relpos_fwd")
-            return None, lse
+            O, lse = seq_ops.relpos_attention_fwd(qkv, tab, B, N, h, tp, ws, shift, save=save)
+            return O, None, lse
         assert not self.split, "split_bf16: no relative-position attention"
-        bias = self._empty(h, N, N, dtype=torch.float32)
-        check(lib.htrvt_relpos_bias_fwd(ptr(tab), ptr(bias), N, s.table_patches, ws, shift, h, N, st), "relpos_bias_fwd")
-        return self._attention_fwd_unfused(qkv, O, B, N, D, h, hd, scale, st, bias=bias), None
+        bias = seq_ops.relpos_bias_fwd(tab, N, tp, ws, shift, N)
+        return (*seq_ops.attention_unfused_fwd(qkv, B, N, h, bias=bias), None)
 
-    def _relpos_attention_bwd(self, P, G, e, dO, dqkv, B, N, D, h, hd, scale, st):
+    def _relpos_attention_bwd(self, P, G, e, dO, B, N):
         """backward of _relpos_attention_fwd; the table gradient is ADDED to G (both routes are reproducible: fixed-order
         sums, no atomics)"""
         s = self.s
+        h, tp = s.heads, s.table_patches
         ws, shift = e["geo"]
         name = e["p"] + ".attn.relative_position_bias_table"
         tab, gt = P[name], G.get(name)
         if e["P"] is None:
-            delta = self._empty(B * h, N, dtype=torch.float32)
-            work = None
-            if gt is not None:
-                work = self._empty(lib.htrvt_attn_relpos_bwd_workspace_floats(B, N, h, s.table_patches, ws, shift),
-                                   dtype=torch.float32)
-            check(lib.htrvt_attn_relpos_bwd(ptr(e["qkv"]), ptr(tab), ptr(e["O"]), ptr(dO), ptr(e["lse"]), ptr(delta), ptr(dqkv),
-                                            ptr(gt), ptr(work), B, N, h, hd, scale, s.table_patches, ws, shift, self.dti, st),
-                  "attn_relpos_bwd")
-            return
+            return seq_ops.relpos_attention_bwd(e["qkv"], tab, e["O"], dO, e["lse"], B, N, h, tp, ws, shift, dtable=gt)
         dbias = torch.zeros(h, N, N, dtype=torch.float32, device=self.dev)
-        self._attention_bwd_unfused(e["qkv"], e["P"], dO, dqkv, B, N, D, h, hd, scale, st, dbias=dbias)
+        dqkv = seq_ops.attention_unfused_bwd(e["qkv"], e["P"], dO, B, N, h, dbias=dbias)
         if gt is not None:
-            dtab = self._empty(*tab.shape, dtype=torch.float32)
-            check(lib.htrvt_relpos_bias_bwd(ptr(dbias), ptr(dtab), N, s.table_patches, ws, shift, h, N, st), "relpos_bias_bwd")
-            check(lib.htrvt_rowsum_f32(ptr(dtab), 1, dtab.numel(), ptr(gt), st), "rowsum")
-
-    def _attention_fwd_unfused(self, qkv, O, B, N, D, h, hd, scale, st, bias=None):
-        """float32 path (and shapes the fused kernel does not serve): S = scale q k^T, row softmax, O = P v as batched
-        GEMMs over the [B,N,3,h,hd] layout; returns P (kept for the backward)"""
-        S = self._empty(B * h, N, N, dtype=torch.float32)
-        gemm(qkv, qkv, S, dtype=self.dtype, M=N, N=N, K=hd, lda=3 * D, ldb=3 * D, ldc=N, batch=B * h, batch_inner=h,
-             sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(h * N * N, N * N), b_off=D, alpha=scale, c_f32=True)
-        Pm = self._empty(B * h, N, N)
-        check(lib.htrvt_softmax_rows(ptr(S), ptr(Pm), B * h * N, N, self.dti, ptr(bias), h * N if bias is not None else 0, st),
-              "softmax_rows")
-        del S
-        gemm(Pm, qkv, O, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * h,
-             batch_inner=h, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * D, hd), b_off=2 * D)
-        return Pm
-
-    def _attention_bwd_unfused(self, qkv, Pm, dO, dqkv, B, N, D, h, hd, scale, st, dbias=None):
-        """float32 path (and shapes the fused kernel does not serve): batched GEMMs + row-softmax backward over the saved P.
-        dbias (window fork, float32 [h, N, N]): += d(score) summed over the batch (the scale then moves into the GEMMs)"""
-        bstr = dict(batch=B * h, batch_inner=h)
-        # dV = P^T dO
-        gemm(Pm, dO, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(h * N * N, N * N), sB=(N * D, hd), sC=(N * 3 * D, hd), c_off=2 * D, **bstr)
-        # dP = dO V^T
-        dP = self._empty(B * h, N, N, dtype=torch.float32)
-        gemm(dO, qkv, dP, dtype=self.dtype, M=N, N=N, K=hd, lda=D, ldb=3 * D, ldc=N, sA=(N * D, hd), sB=(N * 3 * D, hd),
-             sC=(h * N * N, N * N), b_off=2 * D, c_f32=True, **bstr)
-        dS = self._empty(B * h, N, N)
-        s_in, s_out = (scale, 1.0) if dbias is None else (1.0, scale)
-        check(lib.htrvt_softmax_bwd_rows(ptr(Pm), ptr(dP), ptr(dS), B * h * N, N, s_in, self.dti, st), "softmax_bwd_rows")
-        del dP
-        if dbias is not None:
-            ops.colsum(dS, B, h * N * N, h * N * N, dbias, dti=self.dti)
-        # dQ = dS K ; dK = dS^T Q
-        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, b_layout=MNMAJOR, alpha=s_out,
-             sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=D, c_off=0, **bstr)
-        gemm(dS, qkv, dqkv, dtype=self.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, a_layout=MNMAJOR, alpha=s_out,
-             b_layout=MNMAJOR, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=0, c_off=D, **bstr)
-        del dS
+            dtab = seq_ops.relpos_bias_bwd(dbias, N, tp, ws, shift)
+            check(lib.htrvt_rowsum_f32(ptr(dtab), 1, dtab.numel(), ptr(gt), stream()), "rowsum")
+        return dqkv
 
     # ------------------------------------------------------------------ backward
     def backward(self, P, G, dy, after_encoder=None, after_layer3=None, dfeats=None):
@@ -1400,14 +1308,12 @@ class Engine:
         st = stream()
         B, N, D = sv["B"], sv["N"], s.D
         M = B * N
-        h, hd = s.heads, s.hd
-        scale = hd ** -0.5
         dx = self.ln_bwd(dxn, sv["x_last"], sv["mn"], sv["rn"], P["norm.weight"], None, G["norm.weight"], G["norm.bias"])
 
         for e in reversed(sv["enc"]):
             p = e["p"]
             if s.lgp is not None:
-                dx = self._lgp_block_bwd(P, G, e, dx, B, N, st)
+                dx = self._lgp_block_bwd(P, G, e, dx, B, N)
                 continue
             # MLP: x2 = x1 + fc2(gelu(fc1(ln2)))
             dx1 = self._mlp_bwd(P, G, e, dx)
@@ -1415,12 +1321,10 @@ class Engine:
             wp, wpt = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             dO = self.linear_dgrad(dx1, wp, wpt)
             self.linear_wgrad(dx1, e["O"], G[p + ".attn.proj.weight"], G[p + ".attn.proj.bias"])
-            qkv = e["qkv"]
-            dqkv = self._empty(M, 3 * D)
             if e.get("geo") is not None:
-                self._relpos_attention_bwd(P, G, e, dO, dqkv, B, N, D, h, hd, scale, st)
+                dqkv = self._relpos_attention_bwd(P, G, e, dO, B, N)
             else:
-                self._attention_bwd(qkv, e["P"], e["lse"], e["O"], dO, dqkv, B, N, D, h, hd, scale, st)
+                dqkv = self._attention_bwd(e["qkv"], e["P"], e["lse"], e["O"], dO, B, N)
             wq, wqt = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             dln1 = self.linear_dgrad(dqkv, wq, wqt)
             self.linear_wgrad(dqkv, e["ln1"], G[p + ".attn.qkv.weight"], G[p + ".attn.qkv.bias"])

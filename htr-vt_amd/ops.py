@@ -12,8 +12,6 @@ import torch
 from . import _lib
 from ._lib import BF16, F32, GATHER_CONV_DGRAD, GATHER_CONV_FWD, GATHER_CONV_WGRAD, KMAJOR, MNMAJOR, GemmDesc, check, lib
 
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
 # kernel selector of the calls that pass no `tile=` (0: the library's choice); tests set it to run whole convolution
 # paths on one kernel variant (tests/test_gemm8p_gpu.py)
 _ENV_TILE = 0

@@ -1,0 +1,276 @@
+"""The launch sequences of the attention flavours and norms, each written once.
+
+Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
+torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
+destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, and the autograd wrappers of variants.py.
+
+Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5."""
+import torch
+
+from ._lib import check, lib
+from .ops import MNMAJOR, colsum, dt, gemm, ptr, stream
+
+
+def _f32(x, *shape):
+    return torch.empty(*shape, dtype=torch.float32, device=x.device)
+
+
+def _like(x, *shape):
+    return torch.empty(*shape, dtype=x.dtype, device=x.device)
+
+
+def _heads(qkv, h):
+    """(D, hd) of qkv [B*N, 3*D], D = h * hd"""
+    D = qkv.shape[1] // 3
+    return D, D // h
+
+
+# ---- affine LayerNorm --------------------------------------------------------------------------------------------------
+
+def layernorm_fwd(x, gamma, beta, eps, save=True):
+    """x [rows, D] -> (y, mean, rstd); the statistics only under `save`"""
+    rows, D = x.shape
+    y = torch.empty_like(x)
+    mean, rstd = (_f32(x, rows), _f32(x, rows)) if save else (None, None)
+    check(lib.htrvt_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), rows, D, eps, dt(x.dtype),
+                                  stream()), "layernorm_fwd")
+    return y, mean, rstd
+
+
+def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None):
+    """dx (+ dres, the residual branch's gradient); dgamma / dbeta += the ordered column sum of the per-block partials"""
+    rows, D = x.shape
+    nblk = lib.htrvt_layernorm_bwd_blocks(rows)
+    partial = _f32(x, nblk, 2, D)
+    dx = torch.empty_like(x)
+    check(lib.htrvt_layernorm_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx), ptr(partial),
+                                  rows, D, dt(x.dtype), stream()), "layernorm_bwd")
+    if dbeta.data_ptr() == dgamma.data_ptr() + 4 * D:   # weight and bias adjacent in one float32 buffer: one launch
+        colsum(partial, nblk, 2 * D, 2 * D, dgamma, dti=0)
+    else:
+        colsum(partial, nblk, D, 2 * D, dgamma, dti=0)
+        colsum(partial.data_ptr() + 4 * D, nblk, D, 2 * D, dbeta, dti=0)
+    return dx
+
+
+# ---- self-attention, fused (csrc/attention.hip): scores / probabilities stay on chip -----------------------------------
+
+def attention_fwd(qkv, B, N, h, bias=None, save=True):
+    """(out [B*N, D], lse [B*h, N] or None); bias: None or dense float32 [h, N, N]"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * N, D)
+    lse = _f32(qkv, B * h, N) if save else None
+    check(lib.htrvt_attn_fwd(ptr(qkv), ptr(bias), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, dt(qkv.dtype), stream()),
+          "attn_fwd")
+    return out, lse
+
+
+def attention_bwd(qkv, out, dout, lse, B, N, h, bias=None, dbias=None):
+    """dqkv by the recomputing backward; dbias (float32 [h, N, N]) += d(score) summed over the batch"""
+    hd = _heads(qkv, h)[1]
+    dqkv = torch.empty_like(qkv)
+    delta = _f32(qkv, B * h, N)
+    check(lib.htrvt_attn_bwd(ptr(qkv), ptr(bias), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dbias), B, N, h,
+                             hd, hd ** -0.5, dt(qkv.dtype), stream()), "attn_bwd")
+    return dqkv
+
+
+# ---- self-attention as batched GEMMs + row softmax: float32, and shapes the fused kernels do not serve -----------------
+
+def attention_unfused_fwd(qkv, B, N, h, bias=None):
+    """S = scale q k^T, P = softmax(S + bias), out = P v -> (out, P [B*h, N, N], kept for the backward)"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * N, D)
+    S = _f32(qkv, B * h, N, N)
+    gemm(qkv, qkv, S, dtype=qkv.dtype, M=N, N=N, K=hd, lda=3 * D, ldb=3 * D, ldc=N, batch=B * h, batch_inner=h,
+         sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(h * N * N, N * N), b_off=D, alpha=hd ** -0.5, c_f32=True)
+    P = _like(qkv, B * h, N, N)
+    check(lib.htrvt_softmax_rows(ptr(S), ptr(P), B * h * N, N, dt(qkv.dtype), ptr(bias), h * N if bias is not None else 0,
+                                 stream()), "softmax_rows")
+    del S
+    gemm(P, qkv, out, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * h,
+         batch_inner=h, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * D, hd), b_off=2 * D)
+    return out, P
+
+
+def attention_unfused_bwd(qkv, P, dout, B, N, h, dbias=None):
+    """dqkv over the saved P.  Without dbias the score scale goes into the softmax backward; with dbias (float32
+    [h, N, N], += d(score) summed over the batch) dS stays unscaled and the dQ / dK GEMMs carry the scale."""
+    D, hd = _heads(qkv, h)
+    scale = hd ** -0.5
+    dqkv = torch.empty_like(qkv)
+    bstr = dict(batch=B * h, batch_inner=h)
+    # dV = P^T dO
+    gemm(P, dout, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
+         sA=(h * N * N, N * N), sB=(N * D, hd), sC=(N * 3 * D, hd), c_off=2 * D, **bstr)
+    # dP = dO V^T
+    dP = _f32(qkv, B * h, N, N)
+    gemm(dout, qkv, dP, dtype=qkv.dtype, M=N, N=N, K=hd, lda=D, ldb=3 * D, ldc=N, sA=(N * D, hd), sB=(N * 3 * D, hd),
+         sC=(h * N * N, N * N), b_off=2 * D, c_f32=True, **bstr)
+    dS = _like(qkv, B * h, N, N)
+    s_in, s_out = (scale, 1.0) if dbias is None else (1.0, scale)
+    check(lib.htrvt_softmax_bwd_rows(ptr(P), ptr(dP), ptr(dS), B * h * N, N, s_in, dt(qkv.dtype), stream()),
+          "softmax_bwd_rows")
+    del dP
+    if dbias is not None:
+        colsum(dS, B, h * N * N, h * N * N, dbias, dti=dt(qkv.dtype))
+    # dQ = dS K ; dK = dS^T Q
+    gemm(dS, qkv, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, b_layout=MNMAJOR, alpha=s_out,
+         sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=D, c_off=0, **bstr)
+    gemm(dS, qkv, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, a_layout=MNMAJOR, alpha=s_out,
+         b_layout=MNMAJOR, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=0, c_off=D, **bstr)
+    return dqkv
+
+
+# ---- window fork: relative-position table [(2P-1), h] float32, 1-D (shifted) windows -----------------------------------
+
+def relpos_workspace_floats(B, N, h, num_patches, window=0, shift=0):
+    n = lib.htrvt_attn_relpos_bwd_workspace_floats(B, N, h, num_patches, window, shift)
+    if n < 0:
+        raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
+    return n
+
+
+def relpos_attention_fwd(qkv, table, B, N, h, num_patches, window, shift, save=True):
+    """table-driven fused kernels (csrc/attn_relpos.hip, bfloat16): (out, lse or None)"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * N, D)
+    lse = _f32(qkv, B * h, N) if save else None
+    check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(table), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, num_patches, window,
+                                    shift, dt(qkv.dtype), stream()), "attn_relpos_fwd")
+    return out, lse
+
+
+def relpos_attention_bwd(qkv, table, out, dout, lse, B, N, h, num_patches, window, shift, dtable=None):
+    """dqkv; dtable (float32, the table's shape) += the table gradient, None: no table gradient and no workspace"""
+    hd = _heads(qkv, h)[1]
+    dqkv = torch.empty_like(qkv)
+    delta = _f32(qkv, B * h, N)
+    work = None if dtable is None else _f32(qkv, relpos_workspace_floats(B, N, h, num_patches, window, shift))
+    check(lib.htrvt_attn_relpos_bwd(ptr(qkv), ptr(table), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dtable),
+                                    ptr(work), B, N, h, hd, hd ** -0.5, num_patches, window, shift, dt(qkv.dtype), stream()),
+          "attn_relpos_bwd")
+    return dqkv
+
+
+def relpos_bias_fwd(table, N, num_patches, window, shift, ld):
+    """dense float32 bias [h, ld, ld] for the unfused route: table entries inside a window, -1e30 outside and at
+    columns >= N (csrc/variants.hip)"""
+    h = table.shape[1]
+    bias = _f32(table, h, ld, ld)
+    check(lib.htrvt_relpos_bias_fwd(ptr(table), ptr(bias), N, num_patches, window, shift, h, ld, stream()), "relpos_bias_fwd")
+    return bias
+
+
+def relpos_bias_bwd(dbias, N, num_patches, window, shift):
+    """dense d(bias) [h, ld, ld] -> the table's gradient [(2P-1), h] (written, not added: a per-entry gather-sum)"""
+    h, ld = dbias.shape[0], dbias.shape[-1]
+    dtable = _f32(dbias, 2 * num_patches - 1, h)
+    check(lib.htrvt_relpos_bias_bwd(ptr(dbias), ptr(dtable), N, num_patches, window, shift, h, ld, stream()), "relpos_bias_bwd")
+    return dtable
+
+
+# ---- SGM head: single-head cross-attention softmax(Q K^T / sqrt(D)) K, K = V -------------------------------------------
+
+def cross_attention_fwd(Q, KV):
+    """Q [B, L, D], KV [B, N, D] -> (out [B, L, D], P [B, L, N])"""
+    B, L, D = Q.shape
+    N = KV.shape[1]
+    S = _f32(Q, B, L, N)
+    gemm(Q, KV, S, dtype=Q.dtype, M=L, N=N, K=D, lda=D, ldb=D, ldc=N, batch=B, sA=(L * D, 0), sB=(N * D, 0), sC=(L * N, 0),
+         alpha=D ** -0.5, c_f32=True)
+    P = _like(Q, B, L, N)
+    check(lib.htrvt_softmax_rows(ptr(S), ptr(P), B * L, N, dt(Q.dtype), None, 0, stream()), "softmax_rows")
+    out = _like(Q, B, L, D)
+    gemm(P, KV, out, dtype=Q.dtype, M=L, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, batch=B, sA=(L * N, 0),
+         sB=(N * D, 0), sC=(L * D, 0))
+    return out, P
+
+
+def cross_attention_bwd(Q, KV, P, dout):
+    """(dQ, dKV); dKV sums the paths through V (P^T dO) and through K (dS^T Q)"""
+    B, L, D = Q.shape
+    N = KV.shape[1]
+    dtype = Q.dtype
+    bb = dict(batch=B)
+    dP = _f32(Q, B, L, N)
+    gemm(dout, KV, dP, dtype=dtype, M=L, N=N, K=D, lda=D, ldb=D, ldc=N, sA=(L * D, 0), sB=(N * D, 0), sC=(L * N, 0),
+         c_f32=True, **bb)                                                        # dP = dO V^T
+    dS = _like(Q, B, L, N)
+    check(lib.htrvt_softmax_bwd_rows(ptr(P), ptr(dP), ptr(dS), B * L, N, D ** -0.5, dt(dtype), stream()), "softmax_bwd_rows")
+    dQ = torch.empty_like(Q)
+    gemm(dS, KV, dQ, dtype=dtype, M=L, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, sA=(L * N, 0), sB=(N * D, 0),
+         sC=(L * D, 0), **bb)                                                     # dQ = dS K
+    dKV = torch.empty_like(KV)
+    gemm(P, dout, dKV, dtype=dtype, M=N, N=D, K=L, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
+         sA=(L * N, 0), sB=(L * D, 0), sC=(N * D, 0), **bb)                       # through V: P^T dO
+    gemm(dS, Q, dKV, dtype=dtype, M=N, N=D, K=L, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
+         sA=(L * N, 0), sB=(L * D, 0), sC=(N * D, 0), residual=dKV, **bb)         # + through K: dS^T Q
+    return dQ, dKV
+
+
+# ---- LGP fork (csrc/lgp.hip): window-12 attention, pool + LayerNorm, up-sample * sigmoid(alpha) -------------------------
+
+def local_attention_fwd(qkv, qkv_bias, B, N, h, window):
+    """attention inside windows of `window` tokens; the padding slots of a ragged last window are rows equal to the qkv
+    Linear's float32 bias"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * N, D)
+    check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(qkv_bias), ptr(out), B, N, h, hd, window, hd ** -0.5, dt(qkv.dtype), stream()),
+          "attn_local_fwd")
+    return out
+
+
+def local_attention_bwd(qkv, qkv_bias, dout, B, N, h, window):
+    """(dqkv, dpad float32 [B, 2*D]: per image the gradient of the padding rows' k / v, meaningful where N % window; its
+    column sum belongs to the k / v thirds of the bias gradient)"""
+    D, hd = _heads(qkv, h)
+    dqkv = torch.empty_like(qkv)
+    dpad = _f32(qkv, B, 2 * D)
+    check(lib.htrvt_attn_local_bwd(ptr(qkv), ptr(qkv_bias), ptr(dout), ptr(dqkv), ptr(dpad), B, N, h, hd, window, hd ** -0.5,
+                                   dt(qkv.dtype), stream()), "attn_local_bwd")
+    return dqkv, dpad
+
+
+def pool_norm_fwd(x, B, N, G, eps):
+    """average pooling of x [B*N, D] to G tokens per image + LayerNorm without affine -> (z [B*G, D], mean, rstd)"""
+    D = x.shape[1]
+    z = _like(x, B * G, D)
+    mean, rstd = _f32(x, B * G), _f32(x, B * G)
+    check(lib.htrvt_lgp_pool_norm_fwd(ptr(x), ptr(z), ptr(mean), ptr(rstd), B, N, G, D, eps, dt(x.dtype), stream()),
+          "lgp_pool_norm_fwd")
+    return z, mean, rstd
+
+
+def pool_norm_bwd(dz, z, rstd, B, N, G, dx=None):
+    """the gradient of x: a new tensor, or added into `dx` [B*N, D] where one is given"""
+    D = z.shape[1]
+    add = dx is not None
+    if not add:
+        dx = _like(z, B * N, D)
+    ws = _f32(z, 2 * B * G)
+    check(lib.htrvt_lgp_pool_norm_bwd(ptr(dz), ptr(z), ptr(rstd), ptr(ws), ptr(dx), B, N, G, D, int(add), dt(z.dtype), stream()),
+          "lgp_pool_norm_bwd")
+    return dx
+
+
+def upsample_fwd(y, logit_alpha, out, B, N, G):
+    """out [B*N, D] (may be a column block such as cat[:, D:]) = y [B*G, D] linearly interpolated to N tokens per image,
+    times sigmoid(logit_alpha)"""
+    D = y.shape[1]
+    assert out.shape[1] == D and out.stride(1) == 1
+    check(lib.htrvt_lgp_upsample_fwd(ptr(y), ptr(logit_alpha), ptr(out), out.stride(0), B, N, G, D, dt(y.dtype), stream()),
+          "lgp_upsample_fwd")
+    return out
+
+
+def upsample_bwd(dout, y, logit_alpha, dalpha, B, N, G):
+    """dy [B*G, D]; dalpha (0-dim float32) += d logit_alpha.  dout may be a column block, as in upsample_fwd."""
+    D = y.shape[1]
+    assert dout.shape[1] == D and dout.stride(1) == 1
+    dy = torch.empty_like(y)
+    ws = _f32(y, lib.htrvt_lgp_upsample_bwd_workspace_floats(B, G))
+    check(lib.htrvt_lgp_upsample_bwd(ptr(dout), dout.stride(0), ptr(y), ptr(logit_alpha), ptr(dy), ptr(dalpha), ptr(ws), B, N, G,
+                                     D, dt(y.dtype), stream()), "lgp_upsample_bwd")
+    return dy

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 import htrvt_amd                        # noqa: F401  (loads libhtrvt_hip.so or raises)
+from htrvt_amd import seq_ops
 from htrvt_amd._lib import check, lib
 from htrvt_amd.ops import MNMAJOR, colsum, dt, gemm, ptr, stream
 
@@ -79,28 +80,6 @@ def _convert(src, dst, accumulate=False):
     check(lib.htrvt_sgm_convert(ptr(src), dt(src.dtype), ptr(dst), dt(dst.dtype), src.numel(), int(accumulate), stream()),
           "sgm_convert")
     return dst
-
-
-def _ln_fwd(x, gamma, beta, eps):
-    rows, D = x.shape
-    y = torch.empty_like(x)
-    mean, rstd = _empty(rows, torch.float32, x.device), _empty(rows, torch.float32, x.device)
-    check(lib.htrvt_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd), rows, D, eps, dt(x.dtype),
-                                  stream()), "layernorm_fwd")
-    return y, mean, rstd
-
-
-def _ln_bwd(dy, x, mean, rstd, gamma):
-    """(dx, dgamma, dbeta): partial sums per block, then the ordered column sum"""
-    rows, D = x.shape
-    nblk = lib.htrvt_layernorm_bwd_blocks(rows)
-    partial = _empty((nblk, 2, D), torch.float32, x.device)
-    dx = torch.empty_like(x)
-    check(lib.htrvt_layernorm_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), None, ptr(dx), ptr(partial), rows, D,
-                                  dt(x.dtype), stream()), "layernorm_bwd")
-    dgb = torch.zeros(2 * D, dtype=torch.float32, device=x.device)
-    colsum(partial, nblk, 2 * D, 2 * D, dgb, dti=0)
-    return dx, dgb[:D], dgb[D:]
 
 
 def _wgrad(dy, x, rows):
@@ -164,19 +143,12 @@ class _SGMFunction(torch.autograd.Function):
                                       ptr(P["dir_right"].contiguous()), ptr(A), B, L, S, V, dtx, dti, st), "sgm_query_fwd")
         Qp = _empty((R, D), cdt, dev)
         gemm(A, wt, Qp, dtype=cdt, M=R, N=D, K=dtx, lda=dtx, ldb=dtx, ldc=D, bias=P["txt_proj.bias"].contiguous())
-        Q, qm, qr = _ln_fwd(Qp, P["q_norm.weight"].contiguous(), P["q_norm.bias"].contiguous(), head.q_norm.eps)
-        K, km, kr = _ln_fwd(visc.view(B * N, D), P["kv_norm.weight"].contiguous(), P["kv_norm.bias"].contiguous(),
-                            head.kv_norm.eps)
-        # cross-attention of both directions: softmax(Q K^T / sqrt(D)) K, K = V = kv_norm(F)
-        L2, scale = 2 * L, D ** -0.5
-        Sc = _empty((B, L2, N), f32, dev)
-        gemm(Q, K, Sc, dtype=cdt, M=L2, N=N, K=D, lda=D, ldb=D, ldc=N, batch=B, sA=(L2 * D, 0), sB=(N * D, 0),
-             sC=(L2 * N, 0), alpha=scale, c_f32=True)
-        Pm = _empty((B, L2, N), cdt, dev)
-        check(lib.htrvt_softmax_rows(ptr(Sc), ptr(Pm), B * L2, N, dti, None, 0, st), "softmax_rows")
-        O = _empty((R, D), cdt, dev)
-        gemm(Pm, K, O, dtype=cdt, M=L2, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, batch=B, sA=(L2 * N, 0),
-             sB=(N * D, 0), sC=(L2 * D, 0))
+        Q, qm, qr = seq_ops.layernorm_fwd(Qp, P["q_norm.weight"].contiguous(), P["q_norm.bias"].contiguous(), head.q_norm.eps)
+        K, km, kr = seq_ops.layernorm_fwd(visc.view(B * N, D), P["kv_norm.weight"].contiguous(),
+                                          P["kv_norm.bias"].contiguous(), head.kv_norm.eps)
+        # cross-attention of both directions as one [B, 2L] query batch: softmax(Q K^T / sqrt(D)) K, K = V = kv_norm(F)
+        O, Pm = seq_ops.cross_attention_fwd(Q.view(B, 2 * L, D), K.view(B, N, D))
+        O = O.view(R, D)
         seed = None
         if p_drop > 0:
             seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev)     # CUDA default generator, no sync
@@ -207,7 +179,7 @@ class _SGMFunction(torch.autograd.Function):
          kg) = ctx.saved_tensors
         B, N, D, L, S, V, Vp, dtx, p_drop, cdt = ctx.dims
         dti, dev, f32, st = dt(cdt), A.device, torch.float32, stream()
-        R, L2, scale = 2 * B * L, 2 * L, D ** -0.5
+        R = 2 * B * L
         gl = None if glog_l is None else glog_l.contiguous().float()
         gr = None if glog_r is None else glog_r.contiguous().float()
         g = None if gloss is None else gloss.contiguous().float()
@@ -222,23 +194,12 @@ class _SGMFunction(torch.autograd.Function):
             check(lib.htrvt_sgm_dropout(ptr(dOd), ptr(dO), R * D, ptr(seed), p_drop, dti, st), "sgm_dropout")
         else:
             dO = dOd
-        bb = dict(batch=B)
-        dP = _empty((B, L2, N), f32, dev)
-        gemm(dO, K, dP, dtype=cdt, M=L2, N=N, K=D, lda=D, ldb=D, ldc=N, sA=(L2 * D, 0), sB=(N * D, 0), sC=(L2 * N, 0),
-             c_f32=True, **bb)                                                          # dP = dO V^T
-        dS = _empty((B, L2, N), cdt, dev)
-        check(lib.htrvt_softmax_bwd_rows(ptr(Pm), ptr(dP), ptr(dS), B * L2, N, scale, dti, st), "softmax_bwd_rows")
-        dQ = _empty((R, D), cdt, dev)
-        gemm(dS, K, dQ, dtype=cdt, M=L2, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, sA=(L2 * N, 0), sB=(N * D, 0),
-             sC=(L2 * D, 0), **bb)                                                       # dQ = dS K
-        dK = _empty((B * N, D), cdt, dev)
-        gemm(Pm, dO, dK, dtype=cdt, M=N, N=D, K=L2, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(L2 * N, 0), sB=(L2 * D, 0), sC=(N * D, 0), **bb)                        # through V: P^T dO
-        gemm(dS, Q, dK, dtype=cdt, M=N, N=D, K=L2, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(L2 * N, 0), sB=(L2 * D, 0), sC=(N * D, 0), residual=dK, **bb)           # + through K: dS^T Q
-        dvisc, dkg, dkb = _ln_bwd(dK, visc.view(B * N, D), km, kr, kg)
+        dQ, dK = seq_ops.cross_attention_bwd(Q.view(B, 2 * L, D), K.view(B, N, D), Pm, dO.view(B, 2 * L, D))
+        dkn = torch.zeros(2 * D, dtype=f32, device=dev)      # (d weight | d bias) adjacent: one column-sum launch
+        dvisc = seq_ops.layernorm_bwd(dK, visc.view(B * N, D), km, kr, kg, dkn[:D], dkn[D:])
         dvis = dvisc.view(B, N, D) if cdt == f32 else _convert(dvisc, _empty((B, N, D), f32, dev))
-        dQp, dqg, dqb = _ln_bwd(dQ, Qp, qm, qr, qg)
+        dqn = torch.zeros(2 * D, dtype=f32, device=dev)
+        dQp = seq_ops.layernorm_bwd(dQ, Qp, qm, qr, qg, dqn[:D], dqn[D:])
         dwt, dbt = _wgrad(dQp, A, R)
         dA = _empty((R, dtx), cdt, dev)
         gemm(dQp, wt, dA, dtype=cdt, M=R, N=dtx, K=D, lda=D, ldb=dtx, ldc=dtx, b_layout=MNMAJOR)
@@ -247,7 +208,7 @@ class _SGMFunction(torch.autograd.Function):
         ws = _empty(max(lib.htrvt_sgm_query_bwd_workspace_floats(B, L, V, dtx), 1), f32, dev)
         check(lib.htrvt_sgm_query_bwd(ptr(left), ptr(right), ptr(dA), ptr(ws), ptr(demb), ptr(ddl), ptr(ddr), B, L, S, V, dtx,
                                       dti, st), "sgm_query_bwd")
-        grads = (demb, ddl, ddr, dwt, dbt, dqg, dqb, dkg, dkb, dwc[:V], dbc[:V])
+        grads = (demb, ddl, ddr, dwt, dbt, dqn[:D], dqn[D:], dkn[:D], dkn[D:], dwc[:V], dbc[:V])
         return (None, dvis, None, None, None, None, None, None) + grads
 
 

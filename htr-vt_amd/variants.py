@@ -1,30 +1,26 @@
-"""Attention flavours of the reference's variant models on the kernels of the hot path.
+"""Autograd wrappers over seq_ops for callers that hold their own tensors: the tests and tools/.
 
-* model_window (/root/reference/model_window/model/HTR_VT.py:11-62,113-154): self-attention with a learned
-  relative-position bias `table[(key - query) + P - 1, head]`, optionally restricted to 1-D windows of `window_size`
-  tokens over the sequence rolled by `shift_size` (blocks 0 and 1 use windows of 16, shift 0 / 8).  Here: ONE dense
-  additive bias [heads, N, N] -- table entries inside a window, a large negative number outside -- handed to the same
-  fused attention kernels (bfloat16) or to the batched-GEMM + row-softmax path (float32); the gradient of the table is
-  the kernels' dense d(score) summed over the batch and gathered back per table entry.  The bias is built, and its
-  gradient gathered, by HIP kernels (csrc/variants.hip); a sequence that is not a multiple of the window (the
-  reference zero-pads it and masks the padding keys) or of the kernels' 128-token tiles is handled by masked columns.
-* model_sgm_* (/root/reference/model_sgm_2/model/sgm_head.py:118-127): the SGM head's single-head cross-attention
-  softmax(Q K^T / sqrt(D)) K with K = V = the (normalised) visual tokens: batched htrvt_gemm + htrvt_softmax_rows over
-  [B, L, D] queries and [B, N, D] tokens, forward and backward.
-* model_lgp (/root/reference/model_lgp/model/plg.py): the three operators of its local-global block that no kernel of
-  the hot path covers (csrc/lgp.hip): attention in windows of 12 tokens whose padding slots are rows equal to the qkv
-  bias, average pooling + LayerNorm without affine, linear up-sampling times sigmoid(logit_alpha).
-
-The index bookkeeping (which table entry each (query, key) pair uses) is host glue on tensors of heads * N^2 elements;
-all arithmetic over activations runs in the HIP kernels."""
-from __future__ import annotations
-
+The models do not come through here.  The forks run as full drop-ins -- window/, lgp/, sgm/ -- whose engine (engine.py)
+and SGM head (sgm/model/sgm_head.py) call the same seq_ops functions directly, so an operator-level test of a wrapper
+below exercises the launch sequence the models run.  Wrapped: the window fork's relative-position attention (table
+-driven in bfloat16; in float32 ONE dense bias [heads, N, N], table entries inside a window and MASKED outside, into the
+batched-GEMM route), the SGM head's single-head cross-attention, and the LGP block's window-12 attention, pool + norm
+and scaled up-sampling.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
+run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
 import torch
 
-from ._lib import check, lib
-from .ops import KMAJOR, MNMAJOR, colsum, dt, gemm, ptr, stream
+from . import seq_ops
+from ._lib import lib
+from .ops import colsum, dt
+from .seq_ops import relpos_workspace_floats  # noqa: F401  (part of this module's surface)
 
 MASKED = -1.0e30      # "outside the window": finite, so an all-masked key tile cannot produce inf - inf in the online softmax
+
+
+def _need_device(*tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback); the index bookkeeping "
+                           "alone is relative_position_index()")
 
 
 def relative_position_index(N, num_patches, window_size=0, shift_size=0):
@@ -43,45 +39,34 @@ def relative_position_index(N, num_patches, window_size=0, shift_size=0):
     return (slot[None, :] - slot[:, None]) + num_patches - 1, win[None, :] == win[:, None]
 
 
-def _padded_len(N, dtype, hd):
-    """sequence length the attention kernels run at: a multiple of 128 where the fused bfloat16 kernels can serve it (the
-    padding keys carry the bias -1e30, the padding queries are dropped), else a multiple of 8 (16-byte rows of the GEMMs)"""
-    from ._lib import lib as _l
+def padded_len(N, dtype, head_dim):
+    """sequence length the attention kernels run at, the `ld` to build the bias at for biased_self_attention: a multiple
+    of 128 where the fused bfloat16 kernels can serve it (the padding keys carry the bias -1e30, the padding queries are
+    dropped), else a multiple of 8 (16-byte rows of the GEMMs)"""
     n128 = (N + 127) // 128 * 128
-    if dtype == torch.bfloat16 and _l.htrvt_attn_supported(n128, hd, dt(dtype)):
+    if dtype == torch.bfloat16 and lib.htrvt_attn_supported(n128, head_dim, dt(dtype)):
         return n128
     return (N + 7) // 8 * 8
 
 
 class _RelPosBias(torch.autograd.Function):
-    """table [(2P-1), heads] float32 (device) -> dense bias [heads, ld, ld]; both directions are HIP kernels
-    (csrc/variants.hip): lookup + window mask forward, per-entry gather-sum backward (no atomics)"""
+    """table [(2P-1), heads] float32 (device) -> dense bias [heads, ld, ld]: lookup + window mask forward, per-entry
+    gather-sum backward (no atomics)"""
 
     @staticmethod
     def forward(ctx, table, N, num_patches, window_size, shift_size, ld):
-        table = table.contiguous().float()
-        heads = table.shape[1]
-        bias = torch.empty(heads, ld, ld, dtype=torch.float32, device=table.device)
-        check(lib.htrvt_relpos_bias_fwd(ptr(table), ptr(bias), N, num_patches, window_size, shift_size, heads, ld, stream()),
-              "relpos_bias_fwd")
-        ctx.geo = (N, num_patches, window_size, shift_size, heads, ld, tuple(table.shape))
-        return bias
+        ctx.geo = (N, num_patches, window_size, shift_size)
+        return seq_ops.relpos_bias_fwd(table.contiguous().float(), N, num_patches, window_size, shift_size, ld)
 
     @staticmethod
     def backward(ctx, dbias):
-        N, P, ws, shift, heads, ld, tshape = ctx.geo
-        dbias = dbias.contiguous().float()
-        dtable = torch.empty(tshape, dtype=torch.float32, device=dbias.device)
-        check(lib.htrvt_relpos_bias_bwd(ptr(dbias), ptr(dtable), N, P, ws, shift, heads, ld, stream()), "relpos_bias_bwd")
-        return dtable, None, None, None, None, None
+        return seq_ops.relpos_bias_bwd(dbias.contiguous().float(), *ctx.geo), None, None, None, None, None
 
 
 def relative_position_bias(table, N, num_patches, window_size=0, shift_size=0, ld=None):
     """dense float32 [heads, ld, ld] score bias from the learned table [(2 P - 1), heads] (ld >= N: the sequence length the
     attention kernels run at, see biased_self_attention; default N).  Differentiable in the table."""
-    if not table.is_cuda:
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback); the index bookkeeping "
-                           "alone is relative_position_index()")
+    _need_device(table)
     return _RelPosBias.apply(table, N, num_patches, window_size, shift_size, N if ld is None else ld)
 
 
@@ -90,58 +75,25 @@ class _BiasedSelfAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, bias, B, N, heads):
-        D = qkv.shape[1] // 3
-        hd = D // heads
-        scale = hd ** -0.5
-        dti = dt(qkv.dtype)
         qkv, bias = qkv.contiguous(), bias.contiguous().float()
-        out = torch.empty(B * N, D, dtype=qkv.dtype, device=qkv.device)
-        st = stream()
-        if lib.htrvt_attn_supported(N, hd, dti):
-            lse = torch.empty(B * heads, N, dtype=torch.float32, device=qkv.device)
-            check(lib.htrvt_attn_fwd(ptr(qkv), ptr(bias), ptr(out), ptr(lse), B, N, heads, hd, scale, dti, st), "attn_fwd")
-            ctx.save_for_backward(qkv, bias, out, lse)
-            ctx.fused = True
+        ctx.fused = bool(lib.htrvt_attn_supported(N, qkv.shape[1] // 3 // heads, dt(qkv.dtype)))
+        if ctx.fused:
+            out, aux = seq_ops.attention_fwd(qkv, B, N, heads, bias=bias)             # aux = lse
         else:
-            S = torch.empty(B * heads, N, N, dtype=torch.float32, device=qkv.device)
-            gemm(qkv, qkv, S, dtype=qkv.dtype, M=N, N=N, K=hd, lda=3 * D, ldb=3 * D, ldc=N, batch=B * heads, batch_inner=heads,
-                 sA=(N * 3 * D, hd), sB=(N * 3 * D, hd), sC=(heads * N * N, N * N), b_off=D, alpha=scale, c_f32=True)
-            P = torch.empty(B * heads, N, N, dtype=qkv.dtype, device=qkv.device)
-            check(lib.htrvt_softmax_rows(ptr(S), ptr(P), B * heads * N, N, dti, ptr(bias), heads * N, st), "softmax_rows")
-            gemm(P, qkv, out, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * heads,
-                 batch_inner=heads, sA=(heads * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * D, hd), b_off=2 * D)
-            ctx.save_for_backward(qkv, bias, out, P)
-            ctx.fused = False
-        ctx.dims = (B, N, heads, hd, D, scale, dti)
+            out, aux = seq_ops.attention_unfused_fwd(qkv, B, N, heads, bias=bias)     # aux = P
+        ctx.save_for_backward(qkv, bias, out, aux)
+        ctx.dims = (B, N, heads)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, h, hd, D, scale, dti = ctx.dims
         qkv, bias, out, aux = ctx.saved_tensors
         dout = dout.contiguous().to(qkv.dtype)
-        dqkv = torch.empty_like(qkv)
         dbias = torch.zeros_like(bias)
-        st = stream()
         if ctx.fused:
-            delta = torch.empty(B * h, N, dtype=torch.float32, device=qkv.device)
-            check(lib.htrvt_attn_bwd(ptr(qkv), ptr(bias), ptr(out), ptr(dout), ptr(aux), ptr(delta), ptr(dqkv), ptr(dbias), B, N, h,
-                                     hd, scale, dti, st), "attn_bwd")
-            return dqkv, dbias, None, None, None
-        P = aux
-        bstr = dict(batch=B * h, batch_inner=h)
-        gemm(P, dout, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(h * N * N, N * N), sB=(N * D, hd), sC=(N * 3 * D, hd), c_off=2 * D, **bstr)                     # dV = P^T dO
-        dP = torch.empty(B * h, N, N, dtype=torch.float32, device=qkv.device)
-        gemm(dout, qkv, dP, dtype=qkv.dtype, M=N, N=N, K=hd, lda=D, ldb=3 * D, ldc=N, sA=(N * D, hd), sB=(N * 3 * D, hd),
-             sC=(h * N * N, N * N), b_off=2 * D, c_f32=True, **bstr)                                           # dP = dO V^T
-        dS = torch.empty(B * h, N, N, dtype=qkv.dtype, device=qkv.device)          # d(score), the scale goes into the GEMMs
-        check(lib.htrvt_softmax_bwd_rows(ptr(P), ptr(dP), ptr(dS), B * h * N, N, 1.0, dti, st), "softmax_bwd_rows")
-        colsum(dS, B, h * N * N, h * N * N, dbias, dti=dti)                         # d(bias) = sum over the batch
-        gemm(dS, qkv, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, b_layout=MNMAJOR, alpha=scale,
-             sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=D, c_off=0, **bstr)          # dQ = dS K
-        gemm(dS, qkv, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             alpha=scale, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * 3 * D, hd), b_off=0, c_off=D, **bstr)   # dK = dS^T Q
+            dqkv = seq_ops.attention_bwd(qkv, out, dout, aux, *ctx.dims, bias=bias, dbias=dbias)
+        else:
+            dqkv = seq_ops.attention_unfused_bwd(qkv, aux, dout, *ctx.dims, dbias=dbias)
         return dqkv, dbias, None, None, None
 
 
@@ -150,11 +102,10 @@ def biased_self_attention(qkv, bias, B, N, heads):
     with ld >= N (see relative_position_bias; columns >= N must hold -1e30).  bfloat16 with hd in {32, 64, 128}: the fused
     kernels, the sequence zero-padded to a multiple of 128 if it is not one (masked keys, dropped queries); otherwise
     (float32 parity path) batched GEMMs + row softmax at a multiple of 8.  Differentiable in qkv and bias."""
-    if not qkv.is_cuda:
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(qkv)
     D3 = qkv.shape[1]
     hd = D3 // 3 // heads
-    Np = _padded_len(N, qkv.dtype, hd)
+    Np = padded_len(N, qkv.dtype, hd)
     ld = bias.shape[-1]
     if ld != Np:
         if ld != N:
@@ -171,45 +122,25 @@ def biased_self_attention(qkv, bias, B, N, heads):
     return out.view(B, Np, -1)[:, :N].reshape(B * N, -1)
 
 
-def padded_len(N, dtype, head_dim):
-    """the `ld` to build the bias at for biased_self_attention"""
-    return _padded_len(N, dtype, head_dim)
-
-
 class _RelPosSelfAttention(torch.autograd.Function):
     """qkv [B*N, 3*heads*hd] bfloat16 + table [(2P-1), heads] float32 -> out [B*N, heads*hd]: the table-driven fused kernels
     (csrc/attn_relpos.hip), any N >= 32 with no padded copy; the table gradient is reduced without atomics"""
 
     @staticmethod
     def forward(ctx, qkv, table, B, N, heads, num_patches, window, shift):
-        D = qkv.shape[1] // 3
-        hd = D // heads
-        scale = hd ** -0.5
-        dti = dt(qkv.dtype)
         if table.dtype != torch.float32:
             raise TypeError(f"relative-position table: float32 expected (the parameter as stored), got {table.dtype}")
         qkv, table = qkv.contiguous(), table.contiguous()
-        out = torch.empty(B * N, D, dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty(B * heads, N, dtype=torch.float32, device=qkv.device)
-        check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(table), ptr(out), ptr(lse), B, N, heads, hd, scale, num_patches, window,
-                                        shift, dti, stream()), "attn_relpos_fwd")
+        ctx.dims = (B, N, heads, num_patches, window, shift)
+        out, lse = seq_ops.relpos_attention_fwd(qkv, table, *ctx.dims)
         ctx.save_for_backward(qkv, table, out, lse)
-        ctx.dims = (B, N, heads, hd, scale, dti, num_patches, window, shift)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, h, hd, scale, dti, P, ws, shift = ctx.dims
         qkv, table, out, lse = ctx.saved_tensors
-        dout = dout.contiguous().to(qkv.dtype)
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty(B * h, N, dtype=torch.float32, device=qkv.device)
-        dtable, work = None, None
-        if ctx.needs_input_grad[1]:
-            dtable = torch.zeros_like(table)
-            work = torch.empty(relpos_workspace_floats(B, N, h, P, ws, shift), dtype=torch.float32, device=qkv.device)
-        check(lib.htrvt_attn_relpos_bwd(ptr(qkv), ptr(table), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dtable),
-                                        ptr(work), B, N, h, hd, scale, P, ws, shift, dti, stream()), "attn_relpos_bwd")
+        dtable = torch.zeros_like(table) if ctx.needs_input_grad[1] else None
+        dqkv = seq_ops.relpos_attention_bwd(qkv, table, out, dout.contiguous().to(qkv.dtype), lse, *ctx.dims, dtable=dtable)
         return dqkv, dtable, None, None, None, None, None, None
 
 
@@ -218,26 +149,18 @@ def relpos_supported(N, head_dim, dtype, num_patches, window_size=0, shift_size=
     return bool(lib.htrvt_attn_relpos_supported(N, head_dim, dt(dtype), num_patches, window_size, shift_size))
 
 
-def relpos_workspace_floats(B, N, heads, num_patches, window_size=0, shift_size=0):
-    n = lib.htrvt_attn_relpos_bwd_workspace_floats(B, N, heads, num_patches, window_size, shift_size)
-    if n < 0:
-        raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
-    return n
-
-
 def relpos_self_attention(qkv, table, B, N, heads, num_patches, window_size=0, shift_size=0):
     """Attention.forward + Block._attend of the window fork on the qkv Linear's output: softmax(q k^T hd^-0.5 + table
     bias) v with 1-D (shifted) windows, qkv [B*N, 3*heads*hd] (layout [B,N,3,heads,hd]), table [(2P-1), heads] float32.
     bfloat16: the table-driven fused kernels (no dense bias, no padding); float32 (parity path): the dense bias of
     relative_position_bias + batched GEMMs and row softmax (biased_self_attention).  Differentiable in qkv and table."""
-    if not (qkv.is_cuda and table.is_cuda):
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(qkv, table)
     hd = qkv.shape[1] // 3 // heads
     if qkv.dtype == torch.bfloat16:
         if not relpos_supported(N, hd, qkv.dtype, num_patches, window_size, shift_size):
             raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
         return _RelPosSelfAttention.apply(qkv, table, B, N, heads, num_patches, window_size, shift_size)
-    bias = relative_position_bias(table, N, num_patches, window_size, shift_size, ld=_padded_len(N, qkv.dtype, hd))
+    bias = relative_position_bias(table, N, num_patches, window_size, shift_size, ld=padded_len(N, qkv.dtype, hd))
     return biased_self_attention(qkv, bias, B, N, heads)
 
 
@@ -246,52 +169,21 @@ class _CrossAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Q, KV):
-        B, L, D = Q.shape
-        N = KV.shape[1]
-        dtype, dti = Q.dtype, dt(Q.dtype)
         Q, KV = Q.contiguous(), KV.contiguous()
-        scale = D ** -0.5
-        S = torch.empty(B, L, N, dtype=torch.float32, device=Q.device)
-        gemm(Q, KV, S, dtype=dtype, M=L, N=N, K=D, lda=D, ldb=D, ldc=N, batch=B, sA=(L * D, 0), sB=(N * D, 0), sC=(L * N, 0),
-             alpha=scale, c_f32=True)
-        P = torch.empty(B, L, N, dtype=dtype, device=Q.device)
-        check(lib.htrvt_softmax_rows(ptr(S), ptr(P), B * L, N, dti, None, 0, stream()), "softmax_rows")
-        out = torch.empty(B, L, D, dtype=dtype, device=Q.device)
-        gemm(P, KV, out, dtype=dtype, M=L, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, batch=B, sA=(L * N, 0),
-             sB=(N * D, 0), sC=(L * D, 0))
+        out, P = seq_ops.cross_attention_fwd(Q, KV)
         ctx.save_for_backward(Q, KV, P)
-        ctx.scale = scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
         Q, KV, P = ctx.saved_tensors
-        B, L, D = Q.shape
-        N = KV.shape[1]
-        dtype, dti, scale = Q.dtype, dt(Q.dtype), ctx.scale
-        dout = dout.contiguous().to(dtype)
-        bb = dict(batch=B)
-        dP = torch.empty(B, L, N, dtype=torch.float32, device=Q.device)
-        gemm(dout, KV, dP, dtype=dtype, M=L, N=N, K=D, lda=D, ldb=D, ldc=N, sA=(L * D, 0), sB=(N * D, 0), sC=(L * N, 0),
-             c_f32=True, **bb)                                                        # dP = dO V^T
-        dS = torch.empty(B, L, N, dtype=dtype, device=Q.device)
-        check(lib.htrvt_softmax_bwd_rows(ptr(P), ptr(dP), ptr(dS), B * L, N, scale, dti, stream()), "softmax_bwd_rows")
-        dQ = torch.empty_like(Q)
-        gemm(dS, KV, dQ, dtype=dtype, M=L, N=D, K=N, lda=N, ldb=D, ldc=D, b_layout=MNMAJOR, sA=(L * N, 0), sB=(N * D, 0),
-             sC=(L * D, 0), **bb)                                                     # dQ = dS K
-        dKV = torch.empty_like(KV)
-        gemm(P, dout, dKV, dtype=dtype, M=N, N=D, K=L, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(L * N, 0), sB=(L * D, 0), sC=(N * D, 0), **bb)                       # through V: P^T dO
-        gemm(dS, Q, dKV, dtype=dtype, M=N, N=D, K=L, lda=N, ldb=D, ldc=D, a_layout=MNMAJOR, b_layout=MNMAJOR,
-             sA=(L * N, 0), sB=(L * D, 0), sC=(N * D, 0), residual=dKV, **bb)         # + through K: dS^T Q
-        return dQ, dKV
+        return seq_ops.cross_attention_bwd(Q, KV, P, dout.contiguous().to(Q.dtype))
 
 
 def cross_attention(Q, KV):
     """single-head cross-attention of the SGM head: Q [B, L, D] text queries, KV [B, N, D] visual tokens (K = V).
     N and D multiples of 8 (bfloat16) / 4 (float32); any L."""
-    if not (Q.is_cuda and KV.is_cuda):
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(Q, KV)
     return _CrossAttention.apply(Q, KV)
 
 
@@ -304,29 +196,19 @@ class _LocalWindowAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, qkv_bias, B, N, heads, window):
-        D = qkv.shape[1] // 3
-        hd = D // heads
-        dti = dt(qkv.dtype)
         if qkv_bias.dtype != torch.float32:
             raise TypeError(f"qkv bias: float32 expected (the parameter as stored), got {qkv_bias.dtype}")
         qkv, qkv_bias = qkv.contiguous(), qkv_bias.contiguous()
-        out = torch.empty(B * N, D, dtype=qkv.dtype, device=qkv.device)
-        check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(qkv_bias), ptr(out), B, N, heads, hd, window, hd ** -0.5, dti, stream()),
-              "attn_local_fwd")
         ctx.save_for_backward(qkv, qkv_bias)
-        ctx.dims = (B, N, heads, hd, window, dti)
-        return out
+        ctx.dims = (B, N, heads, window)
+        return seq_ops.local_attention_fwd(qkv, qkv_bias, *ctx.dims)
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, heads, hd, window, dti = ctx.dims
+        B, N, _, window = ctx.dims
         qkv, qkv_bias = ctx.saved_tensors
-        D = heads * hd
-        dout = dout.contiguous().to(qkv.dtype)
-        dqkv = torch.empty_like(qkv)
-        dpad = torch.empty(B, 2 * D, dtype=torch.float32, device=qkv.device)
-        check(lib.htrvt_attn_local_bwd(ptr(qkv), ptr(qkv_bias), ptr(dout), ptr(dqkv), ptr(dpad), B, N, heads, hd, window,
-                                       hd ** -0.5, dti, stream()), "attn_local_bwd")
+        D = qkv.shape[1] // 3
+        dqkv, dpad = seq_ops.local_attention_bwd(qkv, qkv_bias, dout.contiguous().to(qkv.dtype), *ctx.dims)
         dbias = None
         if ctx.needs_input_grad[1]:
             dbias = torch.zeros_like(qkv_bias)
@@ -342,8 +224,7 @@ def local_attention_supported(head_dim, window, dtype):
 def local_window_attention(qkv, qkv_bias, B, N, heads, window):
     """WindowMHSA1D of the LGP fork on its qkv Linear's output: attention inside non-overlapping windows of `window` tokens,
     the padding slots of a ragged last window being rows equal to `qkv_bias` (not masked).  Differentiable in both."""
-    if not (qkv.is_cuda and qkv_bias.is_cuda):
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(qkv, qkv_bias)
     if not local_attention_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype):
         raise ValueError(f"window attention: {lib.htrvt_last_error().decode()}")
     return _LocalWindowAttention.apply(qkv, qkv_bias, B, N, heads, window)
@@ -352,67 +233,44 @@ def local_window_attention(qkv, qkv_bias, B, N, heads, window):
 class _PoolNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, B, N, G, eps):
-        D = x.shape[1]
-        dti = dt(x.dtype)
-        x = x.contiguous()
-        z = torch.empty(B * G, D, dtype=x.dtype, device=x.device)
-        mean = torch.empty(B * G, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        check(lib.htrvt_lgp_pool_norm_fwd(ptr(x), ptr(z), ptr(mean), ptr(rstd), B, N, G, D, eps, dti, stream()), "lgp_pool_norm_fwd")
+        z, _, rstd = seq_ops.pool_norm_fwd(x.contiguous(), B, N, G, eps)
         ctx.save_for_backward(z, rstd)
-        ctx.dims = (B, N, G, D, dti)
+        ctx.dims = (B, N, G)
         return z
 
     @staticmethod
     def backward(ctx, dz):
-        B, N, G, D, dti = ctx.dims
         z, rstd = ctx.saved_tensors
-        dz = dz.contiguous().to(z.dtype)
-        dx = torch.empty(B * N, D, dtype=z.dtype, device=z.device)
-        ws = torch.empty(2 * B * G, dtype=torch.float32, device=z.device)
-        check(lib.htrvt_lgp_pool_norm_bwd(ptr(dz), ptr(z), ptr(rstd), ptr(ws), ptr(dx), B, N, G, D, 0, dti, stream()),
-              "lgp_pool_norm_bwd")
-        return dx, None, None, None, None
+        return seq_ops.pool_norm_bwd(dz.contiguous().to(z.dtype), z, rstd, *ctx.dims), None, None, None, None
 
 
 def pool_norm(x, B, N, G, eps=1e-5):
     """PooledGlobalMHSA up to its qkv: adaptive average pooling of x [B*N, D] to G tokens per image, then LayerNorm without
     affine -> [B*G, D]"""
-    if not x.is_cuda:
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(x)
     return _PoolNorm.apply(x, B, N, G, eps)
 
 
 class _UpsampleScale(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, logit_alpha, B, G, N):
-        D = y.shape[1]
-        dti = dt(y.dtype)
         if logit_alpha.dtype != torch.float32:
             raise TypeError(f"logit_alpha: float32 expected (the parameter as stored), got {logit_alpha.dtype}")
         y = y.contiguous()
-        out = torch.empty(B * N, D, dtype=y.dtype, device=y.device)
-        check(lib.htrvt_lgp_upsample_fwd(ptr(y), ptr(logit_alpha), ptr(out), D, B, N, G, D, dti, stream()), "lgp_upsample_fwd")
         ctx.save_for_backward(y, logit_alpha)
-        ctx.dims = (B, N, G, D, dti)
-        return out
+        ctx.dims = (B, N, G)
+        return seq_ops.upsample_fwd(y, logit_alpha, torch.empty(B * N, y.shape[1], dtype=y.dtype, device=y.device), *ctx.dims)
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, G, D, dti = ctx.dims
         y, logit_alpha = ctx.saved_tensors
-        dout = dout.contiguous().to(y.dtype)
-        dy = torch.empty_like(y)
         dalpha = torch.zeros_like(logit_alpha)
-        ws = torch.empty(lib.htrvt_lgp_upsample_bwd_workspace_floats(B, G), dtype=torch.float32, device=y.device)
-        check(lib.htrvt_lgp_upsample_bwd(ptr(dout), D, ptr(y), ptr(logit_alpha), ptr(dy), ptr(dalpha), ptr(ws), B, N, G, D, dti,
-                                         stream()), "lgp_upsample_bwd")
+        dy = seq_ops.upsample_bwd(dout.contiguous().to(y.dtype), y, logit_alpha, dalpha, *ctx.dims)
         return dy, dalpha, None, None, None
 
 
 def upsample_scale(y, logit_alpha, B, G, N):
     """the tail of PooledGlobalMHSA: linear interpolation of y [B*G, D] back to N tokens per image (align_corners=False)
     times sigmoid(logit_alpha), logit_alpha a 0-dim float32 device tensor -> [B*N, D]"""
-    if not (y.is_cuda and logit_alpha.is_cuda):
-        raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback)")
+    _need_device(y, logit_alpha)
     return _UpsampleScale.apply(y, logit_alpha, B, G, N)
