@@ -23,9 +23,7 @@ using namespace htrvt;
 
 namespace {
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-constexpr unsigned OOB = 0x80000000u;
 constexpr int NSTAGE = 3;       // NWAVE (template): 6 waves = 192 output columns per workgroup, 12 = 384 (N >= 384: the pixels are read once per 384 columns)
 
 // one LDS-DMA piece with a scalar byte offset (the stage's first pixel): LDS[lds_addr + 16 lane] <- buffer[voff + soff]
@@ -41,10 +39,6 @@ __device__ __forceinline__ void dma16s(const i32x4_t& rsrc, unsigned lds_addr, u
       : "=&s"(keep)
       : "v"(voff), "s"(lds_addr), "s"(rsrc), "s"(soff)
       : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const char* p) {
-  return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
 }
 
 // KS = K / 32 k-steps (K = Cpad, a multiple of 64); TR = pixels per stage

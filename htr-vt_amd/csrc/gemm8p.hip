@@ -15,9 +15,6 @@ int gemm8p_dispatch_conv(int bn, int gather, int epi, const KParams&, int, hipSt
 
 namespace {
 
-constexpr int E_RES = 1, E_GELU = 2, E_GELUGRAD = 4, E_CSTATS = 8, E_RELUMASK = 16, E_BNB1 = 32, E_BNB2 = 64, E_F32 = 128,
-              E_SCALE_RELU = 256;
-
 int ilog2_exact(int v) {
   if (v <= 0 || (v & (v - 1))) return -1;
   int s = 0;

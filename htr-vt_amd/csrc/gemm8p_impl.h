@@ -32,35 +32,11 @@ using namespace htrvt;
 namespace g8 {
 
 constexpr int BK = 64;
-constexpr unsigned OOB = 0x80000000u;
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef int i32x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// One LDS-DMA piece: 64 lanes x 16 B -> LDS [lds_addr, lds_addr + 1 KiB).  Inline asm: hipcc must not know that this
-// writes LDS (it would order every later ds_read behind it with s_waitcnt vmcnt(0)); the kernel counts the pieces itself.
-__device__ __forceinline__ void dma16(const i32x4_t& rsrc, unsigned lds_addr, unsigned voff) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(lds_addr), "s"(rsrc)
-      : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const char* p) {
-  return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
-}
-
-__device__ __forceinline__ i32x4_t make_rsrc(const char* base) {
-  const unsigned long long ba = (unsigned long long)base;  // raw buffer, stride 0, 2 GiB of records
-  return i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), (int)OOB, 0x00020000};
-}
+using I0 = std::integral_constant<int, 0>;
+using I1 = std::integral_constant<int, 1>;
 
 template <int BN_, int WARPS_M_, int WARPS_N_>
 struct Cfg {
@@ -272,32 +248,157 @@ __device__ __forceinline__ bf16x8_t ldfrag(const char* lds, unsigned off) {
   return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(lds + off));
 }
 
+// the two k-steps of N 16-row K-major operand fragments; rd = the lane's byte offset for k-step 0 of the first one
+template <int N>
+__device__ __forceinline__ void read_kmajor(const char* half, unsigned rd, bf16x8_t (&f)[N][2]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    f[i][0] = ldfrag(half, rd + i * 2048);
+    f[i][1] = ldfrag(half, (rd ^ 64) + i * 2048);
+  }
+}
+
+// one quadrant of the wave's block, both k-steps of a k-tile: c += a x b, "n on the rows" (MFMA a-operand = the B
+// fragments).  ZERO: the first k-step starts from a zero C operand instead of c (the persistent kernel's first k-tile of
+// a tile: the quadrant's previous contents are flushed while this runs, no separate zero fill)
+template <bool ZERO, int MT, int NT>
+__device__ __forceinline__ void mma_quadrant(f32x4_t (&c)[MT][NT], const bf16x8_t (&fb)[NT][2], const bf16x8_t (&fa)[MT][2]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        if (ZERO && s == 0)
+          c[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        else
+          c[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j][s], fa[i][s], c[i][j], 0, 0, 0);
+      }
+}
+
+template <int MT, int NT>
+__device__ __forceinline__ void zero_acc(f32x4_t (&c)[MT][NT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) c[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+}
+
+// block -> tile id: consecutive ids share the A rows (all N tiles of one M tile), ids are dealt to the XCDs in contiguous
+// chunks (blocks b and b + 8 share an XCD), bijective for any tile count
+__device__ __forceinline__ int xcd_tile_id(int b, int ntiles) {
+  const int q = ntiles >> 3, r = ntiles & 7, xcd = b & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+}
+
+// CW = 8 or 12 consecutive bf16 columns of a lane: 16 bytes in q (+ 8 bytes in q2) -> floats, and floats -> one
+// 16-byte (+ one 8-byte) buffer store
+template <int CW>
+__device__ __forceinline__ void unpack_bf16(const i32x4_t& q, const i32x2_t& q2, float (&dst)[CW]) {
+  dst[0] = __uint_as_float((unsigned)q.x << 16); dst[1] = __uint_as_float((unsigned)q.x & 0xffff0000u);
+  dst[2] = __uint_as_float((unsigned)q.y << 16); dst[3] = __uint_as_float((unsigned)q.y & 0xffff0000u);
+  dst[4] = __uint_as_float((unsigned)q.z << 16); dst[5] = __uint_as_float((unsigned)q.z & 0xffff0000u);
+  dst[6] = __uint_as_float((unsigned)q.w << 16); dst[7] = __uint_as_float((unsigned)q.w & 0xffff0000u);
+  if constexpr (CW == 12) {
+    dst[8] = __uint_as_float((unsigned)q2.x << 16); dst[9] = __uint_as_float((unsigned)q2.x & 0xffff0000u);
+    dst[10] = __uint_as_float((unsigned)q2.y << 16); dst[11] = __uint_as_float((unsigned)q2.y & 0xffff0000u);
+  }
+}
+template <int CW, class R>
+__device__ __forceinline__ void store_bf16(const R& rs, unsigned off, const float (&src)[CW]) {
+  i32x4_t q;
+  q.x = (int)pack_bf16x2(src[0], src[1]); q.y = (int)pack_bf16x2(src[2], src[3]);
+  q.z = (int)pack_bf16x2(src[4], src[5]); q.w = (int)pack_bf16x2(src[6], src[7]);
+  __builtin_amdgcn_raw_buffer_store_b128(q, rs, off, 0, 0);
+  if constexpr (CW == 12) {
+    i32x2_t q2;
+    q2.x = (int)pack_bf16x2(src[8], src[9]); q2.y = (int)pack_bf16x2(src[10], src[11]);
+    __builtin_amdgcn_raw_buffer_store_b64(q2, rs, off + 16, 0, 0);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
-// Epilogue feature sets (compile time; the host picks the instantiation, anything else stays on the older kernels)
+// THE 8-PHASE SCHEDULE, stated once: gemm8p_body below (one tile per workgroup, K-major) and gemm8pt_body
+// (gemm8pt_impl.h: MN-major operands) run on all of it; gemm8pp_body (gemm8pp_impl.h: persistent walk) on everything but
+// ktile8p, which it mirrors with its tile-boundary work written in (the reason is stated there).  A body supplies
+//   stageA(xc, bufc) / stageB(yc, bufc): issue the two DMA pieces per wave of the NEXT A / B half tile (xc / yc: which
+//       half; the loaders walk the k-tiles themselves: half 0, half 1, next k-tile ...) into LDS buffer bufc;
+//   readA(xc, bufc) / readB(yc, bufc): read the wave's fragments of A half xc (into fa) / B half yc (into fb[yc]);
+//   mma(xc, yc): acc[xc][yc] += fb[yc] x fa (mma_quadrant);
+//   LGKM1: how many of phase 1's LDS reads may still be outstanding once the b0 reads, issued first, must have returned.
+// Every DMA piece is counted by hand: nothing here may be reordered across a wait, which is what the sched_barriers pin.
 // ---------------------------------------------------------------------------------------------
-constexpr int E_RES = 1;        // + residual (same shape / type as C)
-constexpr int E_GELU = 2;       // exact-erf GELU, pre-activation saved to p.preact when non-null
-constexpr int E_GELUGRAD = 4;   // multiply by GELU'(p.preact)
-constexpr int E_CSTATS = 8;     // per-column sum / sum of squares of the accumulators -> p.colstats (conv forward)
-constexpr int E_RELUMASK = 16;  // C = relu_src > 0 ? value : 0 (after the residual)
-constexpr int E_BNB1 = 32;      // BatchNorm-backward sums against bnb_x[0]
-constexpr int E_BNB2 = 64;      // ... and bnb_x[1]
-constexpr int E_F32 = 128;      // float32 C, plain stores (slab or final), alpha / bias only
-constexpr int E_SCALE_RELU = 256;  // eval-mode BatchNorm folded in: per-column scale (+ bias = shift) and ReLU last (act == 3)
+// prologue: k-tile 0 complete + the three half tiles of k-tile 1 that the steady state has in flight at a k-tile's start
+template <class SA, class SB>
+__device__ __forceinline__ void prologue8p(SA& stageA, SB& stageB, int wave) {
+  stageB(I0{}, I0{});
+  stageA(I0{}, I0{});
+  stageB(I1{}, I0{});
+  stageA(I1{}, I0{});
+  stageB(I0{}, I1{});
+  stageA(I0{}, I1{});
+  stageB(I1{}, I1{});
+  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // all but the three youngest half tiles = k-tile 0 has landed
+  __builtin_amdgcn_s_barrier();
+  if ((wave >> 2) == 1) __builtin_amdgcn_s_barrier();   // group 1 (waves 4-7) runs one barrier behind group 0 from here on
+}
+
+// the multiply half of a phase.  Between its two barriers this group has the matrix pipe and its SIMD partners of the
+// other group run their load section; lgkmcnt(0): the fragments read in this phase's load section are in registers;
+// the sched_barriers keep the compiler from moving MFMAs out of, or loads into, the raised-priority stretch.
+template <class F>
+__device__ __forceinline__ void mfma_phase(F&& mma) {
+  __builtin_amdgcn_s_barrier();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_setprio(1);
+  mma();
+  __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+}
+
+// one k-tile = four phases, multiplied from LDS buffer BUFI (kt = its index)
+template <int BUFI, int LGKM1, class RA, class RB, class SA, class SB, class MMA>
+__device__ __forceinline__ void ktile8p(RA& readA, RB& readB, SA& stageA, SB& stageB, MMA& mma) {
+  using BX = std::integral_constant<int, BUFI>;
+  using BY = std::integral_constant<int, BUFI ^ 1>;
+  // phase 1: b0 then a0; DMA of A half 1 of k-tile kt+1 (other buffer; last read two phases ago)
+  readB(I0{}, BX{});
+  __builtin_amdgcn_sched_barrier(0);
+  readA(I0{}, BX{});
+  __builtin_amdgcn_sched_barrier(0);
+  stageA(I1{}, BY{});
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(LGKM1) : "memory");   // the b0 reads (issued first) have returned: B half 0 may be restaged next phase
+  mfma_phase([&] { mma(I0{}, I0{}); });
+  // phase 2: b1; DMA of B half 0 of k-tile kt+2 (this buffer)
+  readB(I1{}, BX{});
+  __builtin_amdgcn_sched_barrier(0);
+  stageB(I0{}, BX{});
+  mfma_phase([&] { mma(I0{}, I1{}); });
+  // phase 3: a1; DMA of A half 0 of k-tile kt+2
+  readA(I1{}, BX{});
+  __builtin_amdgcn_sched_barrier(0);
+  stageA(I0{}, BX{});
+  mfma_phase([&] { mma(I1{}, I1{}); });
+  // phase 4: DMA of B half 1 of k-tile kt+2; everything older than the last three half tiles has landed = k-tile kt+1
+  stageB(I1{}, BX{});
+  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // the three youngest half tiles (2 pieces per wave each) stay in flight
+  mfma_phase([&] { mma(I1{}, I0{}); });
+}
+
+// drain: group 0 joins group 1's last barrier; then the zero-fill pieces issued past the last k-tile
+__device__ __forceinline__ void drain8p(int wave) {
+  if ((wave >> 2) == 0) __builtin_amdgcn_s_barrier();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
 
 template <class C, int GATHER, int EPI, class P>
 __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
   constexpr int MT = C::MT, NT = C::NT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  // ---- block -> tile: consecutive ids share the A rows (all N tiles of one M tile), ids are dealt to the XCDs in
-  //      contiguous chunks (blocks b and b + 8 share an XCD), bijective for any tile count ----
-  const int ntiles = p.tiles_m * p.tiles_n;
-  int id;
-  {
-    const int q = ntiles >> 3, r = ntiles & 7, xcd = block_x & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (block_x >> 3);
-  }
+  const int id = xcd_tile_id(block_x, p.tiles_m * p.tiles_n);
   const int tile_m = id / p.tiles_n, tile_n = id - tile_m * p.tiles_n;
   const int m0 = tile_m * C::BM, n0 = tile_n * C::BN;
 
@@ -315,7 +416,6 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wave >> 2;                                   // the two staggered groups: SIMD partners are w and w + 4
   const int wr = wave / C::WARPS_N, wc = wave - wr * C::WARPS_N;
 
   ALoader<C, GATHER> la;
@@ -327,11 +427,7 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[x][y][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int y = 0; y < 2; ++y) zero_acc(acc[x][y]);
 
   const int nkt = (kend - kbeg + BK - 1) / BK;
   const unsigned lds0 = lds_addr_of(smem);
@@ -352,96 +448,27 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
     constexpr int Y = decltype(yc)::value, BUFI = decltype(bufc)::value;
     lb.template issue<Y>(p, lds0 + BUFI * C::BUF + (Y ? OB1 : OB0), lds0 + C::SCRATCH, kend, wave);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
 
-  // ---- prologue: k-tile 0 complete + the three half tiles of k-tile 1 the steady state has in flight at a k-tile's start ----
-  stageB(I0{}, I0{});
-  stageA(I0{}, I0{});
-  stageB(I1{}, I0{});
-  stageA(I1{}, I0{});
-  stageB(I0{}, I1{});
-  stageA(I0{}, I1{});
-  stageB(I1{}, I1{});
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (grp == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0 from here on
-
-  bf16x8_t fa[MT][2], fb0[NT][2], fb1[NT][2];
-
-  auto mma = [&](auto xc, auto yc, bf16x8_t (&fbx)[NT][2]) {
+  bf16x8_t fa[MT][2], fb[2][NT][2];
+  auto readA = [&](auto xc, auto bufc) { read_kmajor(smem + decltype(bufc)::value * C::BUF + (decltype(xc)::value ? OA1 : OA0), rdA, fa); };
+  auto readB = [&](auto yc, auto bufc) {
+    constexpr int Y = decltype(yc)::value;
+    read_kmajor(smem + decltype(bufc)::value * C::BUF + (Y ? OB1 : OB0), rdB, fb[Y]);
+  };
+  auto mma = [&](auto xc, auto yc) {
     constexpr int X = decltype(xc)::value, Y = decltype(yc)::value;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[X][Y][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fbx[j][s], fa[i][s], acc[X][Y][i][j], 0, 0, 0);
+    mma_quadrant<false>(acc[X][Y], fb[Y], fa);
   };
-  auto readA = [&](const char* half) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      fa[i][0] = ldfrag(half, rdA + i * 2048);
-      fa[i][1] = ldfrag(half, (rdA ^ 64) + i * 2048);
-    }
-  };
-  auto readB = [&](const char* half, bf16x8_t (&f)[NT][2]) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      f[j][0] = ldfrag(half, rdB + j * 2048);
-      f[j][1] = ldfrag(half, (rdB ^ 64) + j * 2048);
-    }
-  };
-#define G8_MFMA_PHASE(X, Y, FB)                  \
-  __builtin_amdgcn_s_barrier();                  \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_setprio(1);                 \
-  mma(X, Y, FB);                                 \
-  __builtin_amdgcn_s_setprio(0);                 \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_barrier();
-
-  // one k-tile = four phases; BUFI: the LDS buffer it is multiplied from, kt its index
-  auto ktile = [&](auto bufc) {
-    constexpr int BUFI = decltype(bufc)::value;
-    using BX = std::integral_constant<int, BUFI>;
-    using BY = std::integral_constant<int, BUFI ^ 1>;
-    const char* base = smem + BUFI * C::BUF;
-    // phase 1: b0 then a0; DMA of A half 1 of k-tile kt+1 (other buffer; last read two phases ago)
-    readB(base + OB0, fb0);
-    __builtin_amdgcn_sched_barrier(0);
-    readA(base + OA0);
-    __builtin_amdgcn_sched_barrier(0);
-    stageA(I1{}, BY{});
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(MT * 2) : "memory");   // the b0 reads (issued first) have returned: B half 0 may be restaged next phase
-    G8_MFMA_PHASE(I0{}, I0{}, fb0)
-    // phase 2: b1; DMA of B half 0 of k-tile kt+2 (this buffer)
-    readB(base + OB1, fb1);
-    __builtin_amdgcn_sched_barrier(0);
-    stageB(I0{}, BX{});
-    G8_MFMA_PHASE(I0{}, I1{}, fb1)
-    // phase 3: a1; DMA of A half 0 of k-tile kt+2
-    readA(base + OA1);
-    __builtin_amdgcn_sched_barrier(0);
-    stageA(I0{}, BX{});
-    G8_MFMA_PHASE(I1{}, I1{}, fb1)
-    // phase 4: DMA of B half 1 of k-tile kt+2; everything older than the last three half tiles has landed = k-tile kt+1
-    stageB(I1{}, BX{});
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    G8_MFMA_PHASE(I1{}, I0{}, fb0)
-  };
-
+  // the schedule; phase 1 may leave the MT * 2 a0 reads outstanding
+  constexpr int LGKM1 = MT * 2;
+  prologue8p(stageA, stageB, wave);
   int kt = 0;
   for (; kt + 1 < nkt; kt += 2) {
-    ktile(I0{});
-    ktile(I1{});
+    ktile8p<0, LGKM1>(readA, readB, stageA, stageB, mma);
+    ktile8p<1, LGKM1>(readA, readB, stageA, stageB, mma);
   }
-  if (kt < nkt) ktile(I0{});
-#undef G8_MFMA_PHASE
-  if (grp == 0) __builtin_amdgcn_s_barrier();   // group 0 joins group 1's last barrier
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-fill pieces issued past the last k-tile
+  if (kt < nkt) ktile8p<0, LGKM1>(readA, readB, stageA, stageB, mma);
+  drain8p(wave);
 
   // ------------------------------------------------------------------ epilogue: straight from the accumulators
   // lane (g = lane >> 4, j = lane & 15): row m = m0 + x*128 + wr*SM + 16*i + j,
@@ -451,7 +478,6 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
   // conditional loads), i.e. one full memory round trip per store.
   const int g = lane >> 4, jr = lane & 15;
   constexpr int CW = 4 * NT;                    // consecutive columns per lane and (x, y, i)
-  typedef int i32x2_t __attribute__((ext_vector_type(2)));
   auto mk = [](const void* ptr, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, bytes, 0x00020000); };
   const long long cbyte = coff * ((EPI & E_F32) ? 4 : 2);
   const auto rC = mk(p.C + cbyte, OOB);
@@ -462,29 +488,6 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
   auto ldf4 = [&](const auto& rs, unsigned off, float* dst) {   // 4 floats
     const i32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
     dst[0] = __int_as_float(q.x); dst[1] = __int_as_float(q.y); dst[2] = __int_as_float(q.z); dst[3] = __int_as_float(q.w);
-  };
-  auto ldbf = [&](const auto& rs, unsigned off, float (&dst)[CW]) {   // CW bf16 = 16 (+ 8) bytes
-    const i32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-    dst[0] = __uint_as_float((unsigned)q.x << 16); dst[1] = __uint_as_float((unsigned)q.x & 0xffff0000u);
-    dst[2] = __uint_as_float((unsigned)q.y << 16); dst[3] = __uint_as_float((unsigned)q.y & 0xffff0000u);
-    dst[4] = __uint_as_float((unsigned)q.z << 16); dst[5] = __uint_as_float((unsigned)q.z & 0xffff0000u);
-    dst[6] = __uint_as_float((unsigned)q.w << 16); dst[7] = __uint_as_float((unsigned)q.w & 0xffff0000u);
-    if constexpr (CW == 12) {
-      const i32x2_t q2 = __builtin_amdgcn_raw_buffer_load_b64(rs, off + 16, 0, 0);
-      dst[8] = __uint_as_float((unsigned)q2.x << 16); dst[9] = __uint_as_float((unsigned)q2.x & 0xffff0000u);
-      dst[10] = __uint_as_float((unsigned)q2.y << 16); dst[11] = __uint_as_float((unsigned)q2.y & 0xffff0000u);
-    }
-  };
-  auto stbf = [&](const auto& rs, unsigned off, const float (&src)[CW]) {
-    i32x4_t q;
-    q.x = (int)pack_bf16x2(src[0], src[1]); q.y = (int)pack_bf16x2(src[2], src[3]);
-    q.z = (int)pack_bf16x2(src[4], src[5]); q.w = (int)pack_bf16x2(src[6], src[7]);
-    __builtin_amdgcn_raw_buffer_store_b128(q, rs, off, 0, 0);
-    if constexpr (CW == 12) {
-      i32x2_t q2;
-      q2.x = (int)pack_bf16x2(src[8], src[9]); q2.y = (int)pack_bf16x2(src[10], src[11]);
-      __builtin_amdgcn_raw_buffer_store_b64(q2, rs, off + 16, 0, 0);
-    }
   };
   // per-column bias: Linear layers, and the folded BatchNorm shift of an eval-mode conv forward; per-column scale: the latter only
   constexpr bool HAS_BIAS = GATHER == 0 || (EPI & E_SCALE_RELU);
@@ -532,18 +535,7 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
     i32x4_t q[NSIDE > 0 ? NSIDE : 1][2];
     i32x2_t q2[NSIDE > 0 ? NSIDE : 1][2];
   };
-  auto unpack = [&](const Raw& r, int sidx, int y, float (&dst)[CW]) {
-    const i32x4_t q = r.q[sidx][y];
-    dst[0] = __uint_as_float((unsigned)q.x << 16); dst[1] = __uint_as_float((unsigned)q.x & 0xffff0000u);
-    dst[2] = __uint_as_float((unsigned)q.y << 16); dst[3] = __uint_as_float((unsigned)q.y & 0xffff0000u);
-    dst[4] = __uint_as_float((unsigned)q.z << 16); dst[5] = __uint_as_float((unsigned)q.z & 0xffff0000u);
-    dst[6] = __uint_as_float((unsigned)q.w << 16); dst[7] = __uint_as_float((unsigned)q.w & 0xffff0000u);
-    if constexpr (CW == 12) {
-      const i32x2_t q2 = r.q2[sidx][y];
-      dst[8] = __uint_as_float((unsigned)q2.x << 16); dst[9] = __uint_as_float((unsigned)q2.x & 0xffff0000u);
-      dst[10] = __uint_as_float((unsigned)q2.y << 16); dst[11] = __uint_as_float((unsigned)q2.y & 0xffff0000u);
-    }
-  };
+  auto unpack = [&](const Raw& r, int sidx, int y, float (&dst)[CW]) { unpack_bf16(r.q[sidx][y], r.q2[sidx][y], dst); };
   const auto rBx0 = mk(NBN > 0 ? p.bnb_x[0] + cbyte : nullptr, NBN > 0 ? OOB : 0u);
   const auto rBx1 = mk(NBN > 1 ? p.bnb_x[1] + cbyte : nullptr, NBN > 1 ? OOB : 0u);
   auto request = [&](int it, Raw& r) {
@@ -626,7 +618,7 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
         if constexpr (EPI & E_GELU) {
           // the saved pre-activation is the bf16-rounded value and GELU is taken of that rounded value, so that the
           // backward's GELU'(saved) belongs to exactly the function the forward applied
-          stbf(rPre, ob, v);
+          store_bf16(rPre, ob, v);
 #pragma unroll
           for (int e = 0; e < CW; e += 2) {
             const unsigned w = pack_bf16x2(v[e], v[e + 1]);
@@ -672,7 +664,7 @@ __device__ __forceinline__ void gemm8p_body(const P& p, const int block_x) {
             for (int e = 0; e < CW; ++e) sums[1 + t][y][e] += gq[e] * xs[e];
           }
         }
-        stbf(rC, ob, v);
+        store_bf16(rC, ob, v);
       }
     }
   };

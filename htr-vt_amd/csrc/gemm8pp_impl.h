@@ -45,11 +45,10 @@ struct PCfg {
 // workgroup-uniform walk over the tiles: virtual block vb -> (m0, n0), the XCD-chunked order of gemm8p_body (blocks b and
 // b + 8 share an XCD; gridDim.x is a multiple of 8, so vb and vb + gridDim.x do too)
 struct TileWalk {
-  int ntiles, tiles_n, q, r;
+  int ntiles, tiles_n;
   __device__ __forceinline__ bool at(int vb, int& m0, int& n0) const {
     if (vb >= ntiles) return false;
-    const int xcd = vb & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (vb >> 3);
+    const int id = xcd_tile_id(vb, ntiles);
     const int tm = id / tiles_n;
     m0 = tm * 256;
     n0 = (id - tm * tiles_n);
@@ -153,13 +152,11 @@ struct Side {
 template <class C, int MODE>
 struct SideOn {
   static constexpr int MT = C::MT, CW = 4 * C::NT;
-  typedef int i32x2_t __attribute__((ext_vector_type(2)));
   i32x4_t q[2][MT];
   i32x2_t q2[2][MT];
   i32x4_t rsrc;
   __device__ __forceinline__ void init(const void* residual) {
-    const unsigned long long ba = (unsigned long long)residual;
-    rsrc = i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), residual != nullptr ? (int)OOB : 0, 0x00020000};
+    rsrc = make_rsrc(residual, residual != nullptr ? OOB : 0u);
   }
   // request quadrant (X, Y) of the tile at (tm0, tn0) into slot SL: inline asm, invisible to the compiler's wait counting
   template <int SL, int X, int Y>
@@ -188,17 +185,8 @@ struct SideOn {
   }
   template <int SL>
   __device__ __forceinline__ void add(int i, float* v) {
-    const i32x4_t a = q[SL][i];
     float x[CW];
-    x[0] = __uint_as_float((unsigned)a.x << 16); x[1] = __uint_as_float((unsigned)a.x & 0xffff0000u);
-    x[2] = __uint_as_float((unsigned)a.y << 16); x[3] = __uint_as_float((unsigned)a.y & 0xffff0000u);
-    x[4] = __uint_as_float((unsigned)a.z << 16); x[5] = __uint_as_float((unsigned)a.z & 0xffff0000u);
-    x[6] = __uint_as_float((unsigned)a.w << 16); x[7] = __uint_as_float((unsigned)a.w & 0xffff0000u);
-    if constexpr (CW == 12) {
-      const i32x2_t b = q2[SL][i];
-      x[8] = __uint_as_float((unsigned)b.x << 16); x[9] = __uint_as_float((unsigned)b.x & 0xffff0000u);
-      x[10] = __uint_as_float((unsigned)b.y << 16); x[11] = __uint_as_float((unsigned)b.y & 0xffff0000u);
-    }
+    unpack_bf16(q[SL][i], q2[SL][i], x);
     if constexpr (MODE == 1) {
 #pragma unroll
       for (int e = 0; e < CW; ++e) v[e] += x[e];
@@ -233,7 +221,6 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wave >> 2;
   const int wr = wave / C::WARPS_N, wc = wave - wr * C::WARPS_N;
   const int stride = (int)gridDim.x;
   const int pM = p.M, pN = p.N;
@@ -241,8 +228,6 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
   TileWalk tw;
   tw.ntiles = p.tiles_m * p.tiles_n;
   tw.tiles_n = p.tiles_n;
-  tw.q = tw.ntiles >> 3;
-  tw.r = tw.ntiles & 7;
 
   PLoadA<C> la;
   PLoadB<C> lb;
@@ -272,38 +257,21 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
     constexpr int Y = decltype(yc)::value, BUFI = decltype(bufc)::value;
     lb.template issue<Y>(p, tw, lds0 + BUFI * C::BUF + (Y ? OB1 : OB0), lds0 + C::SCRATCH, wave, lane, stride);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
 
   // ---- epilogue pieces ----
   const int g = lane >> 4, jr = lane & 15;
   auto mk = [](const void* ptr, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, bytes, 0x00020000); };
   const auto rC = mk(p.C, OOB);
   const auto rPre = mk(p.preact, p.preact != nullptr ? OOB : 0u);
-  const i32x4_t rBias = [&] {
-    const unsigned long long ba = (unsigned long long)p.bias;    // NULL: zero records -> every lane reads 0
-    return i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), p.bias != nullptr ? p.N * 4 : 0, 0x00020000};
-  }();
+  const i32x4_t rBias = make_rsrc(p.bias, p.bias != nullptr ? (unsigned)p.N * 4u : 0u);    // NULL: zero records -> every lane reads 0
   const float alpha = p.alpha;
   const unsigned ldc = (unsigned)p.ldc;
   const char* bias_slot = smem + PCfg<C>::BIAS_OFF + wave * 1024;
-  typedef int i32x2_t __attribute__((ext_vector_type(2)));
   constexpr int NQ = MT * (CW == 12 ? 2 : 1) * ((EPI & E_GELU) ? 2 : 1);     // store instructions of one quadrant flush
   constexpr int NL = RES ? MT * (CW == 12 ? 2 : 1) : 0;                      // load instructions of one quadrant's residual
   Side<C, (EPI & E_RES) ? 1 : ((EPI & E_GELUGRAD) ? 2 : 0)> side;
   side.init((EPI & E_GELUGRAD) ? (const void*)p.preact : (const void*)p.residual);
 
-  auto stbf = [&](const auto& rs, unsigned off, const float (&src)[CW]) {
-    i32x4_t q;
-    q.x = (int)pack_bf16x2(src[0], src[1]); q.y = (int)pack_bf16x2(src[2], src[3]);
-    q.z = (int)pack_bf16x2(src[4], src[5]); q.w = (int)pack_bf16x2(src[6], src[7]);
-    __builtin_amdgcn_raw_buffer_store_b128(q, rs, off, 0, 0);
-    if constexpr (CW == 12) {
-      i32x2_t q2;
-      q2.x = (int)pack_bf16x2(src[8], src[9]); q2.y = (int)pack_bf16x2(src[10], src[11]);
-      __builtin_amdgcn_raw_buffer_store_b64(q2, rs, off + 16, 0, 0);
-    }
-  };
   // the bias of tile (.., n0) -> this wave's LDS slot: float f = y*SN + c of the slot is column n0 + y*HN + wc*SN + c
   auto stage_bias = [&](int n0) {
     const int f = 4 * lane;
@@ -334,7 +302,7 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
 #pragma unroll
         for (int rg = 0; rg < 4; ++rg) v[4 * t + rg] = acc[X][Y][i][t][rg] * alpha + bv[4 * t + rg];
       if constexpr (EPI & E_GELU) {
-        stbf(rPre, ob, v);       // (a NULL preact: zero-record descriptor, the stores are dropped but still counted)
+        store_bf16(rPre, ob, v);       // (a NULL preact: zero-record descriptor, the stores are dropped but still counted)
 #pragma unroll
         for (int e = 0; e < CW; e += 2) {
           const unsigned w = pack_bf16x2(v[e], v[e + 1]);
@@ -344,79 +312,43 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
         }
       }
       side.template add<SL>(i, v);       // E_RES: + residual, in float32: the sum is rounded once (as gemm8p_kernel does)
-      stbf(rC, ob, v);
+      store_bf16(rC, ob, v);
     }
   };
 
-  // ---- prologue (once per workgroup): k-tile 0 complete + three half tiles of k-tile 1 ----
-  stageB(I0{}, I0{});
-  stageA(I0{}, I0{});
-  stageB(I1{}, I0{});
-  stageA(I1{}, I0{});
-  stageB(I0{}, I1{});
-  stageA(I0{}, I1{});
-  stageB(I1{}, I1{});
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (grp == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0 for the whole launch
+  prologue8p(stageA, stageB, wave);   // once per workgroup: the two groups stay one barrier apart for the whole launch
 
-  bf16x8_t fa[MT][2], fb0[NT][2], fb1[NT][2];
-
-  auto mma = [&](auto xc, auto yc, auto zc, bf16x8_t (&fbx)[NT][2]) {
+  bf16x8_t fa[MT][2], fb[2][NT][2];
+  auto readA = [&](auto xc, auto bufc) { read_kmajor(smem + decltype(bufc)::value * C::BUF + (decltype(xc)::value ? OA1 : OA0), rdA, fa); };
+  auto readB = [&](auto yc, auto bufc) {
+    constexpr int Y = decltype(yc)::value;
+    read_kmajor(smem + decltype(bufc)::value * C::BUF + (Y ? OB1 : OB0), rdB, fb[Y]);
+  };
+  auto mma = [&](auto xc, auto yc, auto zc) {
     constexpr int X = decltype(xc)::value, Y = decltype(yc)::value;
-    constexpr bool ZERO = decltype(zc)::value != 0;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          if (ZERO && s == 0)
-            acc[X][Y][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fbx[j][s], fa[i][s], f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          else
-            acc[X][Y][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fbx[j][s], fa[i][s], acc[X][Y][i][j], 0, 0, 0);
-        }
+    mma_quadrant<decltype(zc)::value>(acc[X][Y], fb[Y], fa);
   };
-  auto readA = [&](const char* half) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      fa[i][0] = ldfrag(half, rdA + i * 2048);
-      fa[i][1] = ldfrag(half, (rdA ^ 64) + i * 2048);
-    }
-  };
-  auto readB = [&](const char* half, bf16x8_t (&f)[NT][2]) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      f[j][0] = ldfrag(half, rdB + j * 2048);
-      f[j][1] = ldfrag(half, (rdB ^ 64) + j * 2048);
-    }
-  };
-#define G8P_MFMA_PHASE(X, Y, Z, FB)              \
-  __builtin_amdgcn_s_barrier();                  \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_setprio(1);                 \
-  mma(X, Y, Z, FB);                              \
-  __builtin_amdgcn_s_setprio(0);                 \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_barrier();
 
-  // one k-tile = four phases (gemm8p_body's schedule); KIND adds the tile-boundary work to the load sections
+  // one k-tile = four phases: this MIRRORS ktile8p (gemm8p_impl.h) statement for statement -- same reads, stages, waits
+  // and sched_barriers in the same order, through the same readA / readB / stageA / stageB / mma / mfma_phase -- with the
+  // tile-boundary work of KIND written into the load sections, the zero C operand of the k-tile that opens a tile, and the
+  // longer phase-4 count of the flush k-tile.  It is not routed through ktile8p: with that work supplied to ktile8p as
+  // hooks every instantiation of this kernel came out at 255-256 VGPRs and three of the five spilled
+  // (profiles/gemm8p_one_schedule.md).  A change to the schedule there has to be repeated here.
   auto ktile = [&](auto bufc, auto kindc, int pm0, int pn0, int n0, int m0 = 0) {
     constexpr int BUFI = decltype(bufc)::value, KIND = decltype(kindc)::value;
     using BX = std::integral_constant<int, BUFI>;
     using BY = std::integral_constant<int, BUFI ^ 1>;
-    using Z = std::integral_constant<int, (KIND == KT_OPEN || KIND == KT_FLUSH) ? 1 : 0>;
-    const char* base = smem + BUFI * C::BUF;
+    using Z = std::integral_constant<bool, KIND == KT_OPEN || KIND == KT_FLUSH>;
     // phase 1
     if constexpr (KIND == KT_SIDE) {                    // older than this k-tile's DMA pieces: its phase-4 wait retires them
       side.template load<0, 0, 0>(m0, n0, pM, pN, ldc, wr, wc, g, jr, 0);
       side.template load<1, 0, 1>(m0, n0, pM, pN, ldc, wr, wc, g, jr, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    readB(base + OB0, fb0);
+    readB(I0{}, BX{});
     __builtin_amdgcn_sched_barrier(0);
-    readA(base + OA0);
+    readA(I0{}, BX{});
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (KIND == KT_BIAS) stage_bias(n0);      // older than the three half tiles the phase-4 wait leaves in flight
     stageA(I1{}, BY{});
@@ -430,9 +362,9 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    G8P_MFMA_PHASE(I0{}, I0{}, Z{}, fb0)
+    mfma_phase([&] { mma(I0{}, I0{}, Z{}); });
     // phase 2
-    readB(base + OB1, fb1);
+    readB(I1{}, BX{});
     __builtin_amdgcn_sched_barrier(0);
     stageB(I0{}, BX{});
     if constexpr (KIND == KT_FLUSH) {
@@ -444,9 +376,9 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    G8P_MFMA_PHASE(I0{}, I1{}, Z{}, fb1)
+    mfma_phase([&] { mma(I0{}, I1{}, Z{}); });
     // phase 3
-    readA(base + OA1);
+    readA(I1{}, BX{});
     __builtin_amdgcn_sched_barrier(0);
     stageA(I0{}, BX{});
     if constexpr (KIND == KT_FLUSH) {
@@ -456,7 +388,7 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
       flush(I1{}, I1{}, pm0, pn0, g, jr, I0{});
       __builtin_amdgcn_sched_barrier(0);
     }
-    G8P_MFMA_PHASE(I1{}, I1{}, Z{}, fb1)
+    mfma_phase([&] { mma(I1{}, I1{}, Z{}); });
     // phase 4
     if constexpr (KIND == KT_FLUSH) {
       // younger than the request of quadrant (1, 0): phase 3's two DMA pieces and NQ stores
@@ -475,7 +407,7 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
       side.template wait<0, 6>();
       side.template wait<1, 6>();
     }
-    G8P_MFMA_PHASE(I1{}, I0{}, Z{}, fb0)
+    mfma_phase([&] { mma(I1{}, I0{}, Z{}); });
   };
   using KP = std::integral_constant<int, KT_PLAIN>;
   using KO = std::integral_constant<int, KT_OPEN>;
@@ -511,9 +443,7 @@ __device__ __forceinline__ void gemm8pp_body(const P& p) {
     pn0 = n0;
     first = false;
   }
-#undef G8P_MFMA_PHASE
-  if (grp == 0) __builtin_amdgcn_s_barrier();   // group 0 joins group 1's last barrier
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the zero-fill pieces issued past the last tile
+  drain8p(wave);
   __builtin_amdgcn_sched_barrier(0);
   // the workgroup's last tile: nothing left to hide it under
   int lane_f = lane;

@@ -70,12 +70,7 @@ __device__ __forceinline__ void gemm8pt_body(const P& p, const int block_x) {
   constexpr int MT = C::MT, NT = C::NT;      // 4 x 2 MFMA tiles per quadrant
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int ntiles = p.tiles_m * p.tiles_n;
-  int id;
-  {
-    const int q = ntiles >> 3, r = ntiles & 7, xcd = block_x & 7;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (block_x >> 3);
-  }
+  const int id = xcd_tile_id(block_x, p.tiles_m * p.tiles_n);
   const int tile_m = id / p.tiles_n, tile_n = id - tile_m * p.tiles_n;
   const int m0 = tile_m * C::BM, n0 = tile_n * C::BN;
   const int z = blockIdx.z;
@@ -84,7 +79,6 @@ __device__ __forceinline__ void gemm8pt_body(const P& p, const int block_x) {
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int grp = wave >> 2;
   const int wr = wave / C::WARPS_N, wc = wave - wr * C::WARPS_N;
 
   TLoad la, lb;
@@ -95,11 +89,7 @@ __device__ __forceinline__ void gemm8pt_body(const P& p, const int block_x) {
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[x][y][i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int y = 0; y < 2; ++y) zero_acc(acc[x][y]);
 
   const int nkt = (kend - kbeg + BK - 1) / BK;
   const unsigned lds0 = lds_addr_of(smem);
@@ -136,93 +126,40 @@ __device__ __forceinline__ void gemm8pt_body(const P& p, const int block_x) {
     constexpr int Y = decltype(yc)::value, BUFI = decltype(bufc)::value;
     lb.template issue<Y>(lds0 + BUFI * C::BUF + (Y ? OB1 : OB0), kend, wave);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
 
-  // ---- prologue (gemm8p_body's): k-tile 0 complete + three half tiles of k-tile 1 ----
-  stageB(I0{}, I0{});
-  stageA(I0{}, I0{});
-  stageB(I1{}, I0{});
-  stageA(I1{}, I0{});
-  stageB(I0{}, I1{});
-  stageA(I0{}, I1{});
-  stageB(I1{}, I1{});
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (grp == 1) __builtin_amdgcn_s_barrier();
-
-  bf16x8_t fa[MT][2], fb0[NT][2], fb1[NT][2];
-  auto mma = [&](auto xc, auto yc, bf16x8_t (&fbx)[NT][2]) {
-    constexpr int X = decltype(xc)::value, Y = decltype(yc)::value;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[X][Y][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fbx[j][s], fa[i][s], acc[X][Y][i][j], 0, 0, 0);
-  };
-  auto readA = [&](const char* half) {
+  bf16x8_t fa[MT][2], fb[2][NT][2];
+  auto readA = [&](auto xc, auto bufc) {
+    const char* half = smem + decltype(bufc)::value * C::BUF + (decltype(xc)::value ? OA1 : OA0);
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       fa[i][0] = ldtr(half, rdA[i]);
       fa[i][1] = ldtr(half, rdA[i] + 32 * 256);
     }
   };
-  auto readB = [&](const char* half, bf16x8_t (&f)[NT][2]) {
+  auto readB = [&](auto yc, auto bufc) {
+    constexpr int Y = decltype(yc)::value;
+    const char* half = smem + decltype(bufc)::value * C::BUF + (Y ? OB1 : OB0);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
-      f[j][0] = ldtr(half, rdB[j]);
-      f[j][1] = ldtr(half, rdB[j] + 32 * 256);
+      fb[Y][j][0] = ldtr(half, rdB[j]);
+      fb[Y][j][1] = ldtr(half, rdB[j] + 32 * 256);
     }
   };
-#define G8T_MFMA_PHASE(X, Y, FB)                 \
-  __builtin_amdgcn_s_barrier();                  \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_setprio(1);                 \
-  mma(X, Y, FB);                                 \
-  __builtin_amdgcn_s_setprio(0);                 \
-  __builtin_amdgcn_sched_barrier(0);             \
-  __builtin_amdgcn_s_barrier();
-
-  auto ktile = [&](auto bufc) {
-    constexpr int BUFI = decltype(bufc)::value;
-    using BX = std::integral_constant<int, BUFI>;
-    using BY = std::integral_constant<int, BUFI ^ 1>;
-    const char* base = smem + BUFI * C::BUF;
-    // phase 1: b0 (2 reads per fragment: 8), then a0 (16); DMA of A half 1 of k-tile kt+1
-    readB(base + OB0, fb0);
-    __builtin_amdgcn_sched_barrier(0);
-    readA(base + OA0);
-    __builtin_amdgcn_sched_barrier(0);
-    stageA(I1{}, BY{});
-    asm volatile("s_waitcnt lgkmcnt(15)" ::: "memory");   // 24 reads were issued and at most 15 can be outstanding: the 8 b0 reads (issued first) have returned, B half 0 may be restaged next phase
-    G8T_MFMA_PHASE(I0{}, I0{}, fb0)
-    // phase 2: b1; DMA of B half 0 of k-tile kt+2
-    readB(base + OB1, fb1);
-    __builtin_amdgcn_sched_barrier(0);
-    stageB(I0{}, BX{});
-    G8T_MFMA_PHASE(I0{}, I1{}, fb1)
-    // phase 3: a1; DMA of A half 0 of k-tile kt+2
-    readA(base + OA1);
-    __builtin_amdgcn_sched_barrier(0);
-    stageA(I0{}, BX{});
-    G8T_MFMA_PHASE(I1{}, I1{}, fb1)
-    // phase 4: DMA of B half 1 of k-tile kt+2; k-tile kt+1 has landed
-    stageB(I1{}, BX{});
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    G8T_MFMA_PHASE(I1{}, I0{}, fb0)
+  auto mma = [&](auto xc, auto yc) {
+    constexpr int X = decltype(xc)::value, Y = decltype(yc)::value;
+    mma_quadrant<false>(acc[X][Y], fb[Y], fa);
   };
+  // the schedule of gemm8p_impl.h.  Phase 1 reads b0 with 8 ds_reads (2 per fragment), then a0 with 16: lgkmcnt(15) -- 24
+  // reads were issued and at most 15 can be outstanding (the counter's range), so the 8 b0 reads, issued first, have returned
+  constexpr int LGKM1 = 15;
+  prologue8p(stageA, stageB, wave);
   int kt = 0;
   for (; kt + 1 < nkt; kt += 2) {
-    ktile(I0{});
-    ktile(I1{});
+    ktile8p<0, LGKM1>(readA, readB, stageA, stageB, mma);
+    ktile8p<1, LGKM1>(readA, readB, stageA, stageB, mma);
   }
-  if (kt < nkt) ktile(I0{});
-#undef G8T_MFMA_PHASE
-  if (grp == 0) __builtin_amdgcn_s_barrier();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (kt < nkt) ktile8p<0, LGKM1>(readA, readB, stageA, stageB, mma);
+  drain8p(wave);
 
   // ---- epilogue: lane (g = l >> 4, jr = l & 15) holds C[m0 + x*128 + wr*SM + 16 i + jr][n0 + y*128 + wc*SN + 16 j + 4 g .. + 3] ----
   const int g = lane >> 4, jr = lane & 15;

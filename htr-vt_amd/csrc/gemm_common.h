@@ -10,6 +10,54 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------------------------------------
+// LDS-DMA primitives of the bfloat16 kernels (gemm_dma_impl.h and the halo / hwgrad kernels on it, gemm8p_impl.h, conv1x1.hip)
+// ---------------------------------------------------------------------------------------------
+// a buffer byte offset >= 2^31 is out of range of every descriptor here (all operands are < 2 GiB): loads deliver zeros, stores are dropped
+constexpr unsigned OOB = 0x80000000u;
+
+// One LDS-DMA piece: 64 lanes x 16 B -> LDS [lds_addr, lds_addr + 1 KiB).  Inline asm on purpose: hipcc must not know
+// that this writes LDS -- it would order every later ds_read behind the DMA with s_waitcnt vmcnt(0) (it cannot prove the
+// LDS stages disjoint), which serialises load and MFMA.  The kernels count these pieces themselves (counted vmcnt waits).
+__device__ __forceinline__ void dma16(const i32x4_t& rsrc, unsigned lds_addr, unsigned voff) {
+  unsigned keep;
+  asm volatile(
+      "s_nop 4\n\t"
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(lds_addr), "s"(rsrc)
+      : "memory");
+}
+
+__device__ __forceinline__ unsigned lds_addr_of(const char* p) {
+  return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
+}
+
+// raw buffer, stride 0, `records` bytes (default: the 2 GiB every offset test relies on; 0: every load reads zeros)
+__device__ __forceinline__ i32x4_t make_rsrc(const void* base, unsigned records = OOB) {
+  const unsigned long long ba = (unsigned long long)base;
+  return i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), (int)records, 0x00020000};
+}
+
+// ---------------------------------------------------------------------------------------------
+// Epilogue feature sets of the 8-phase kernels (gemm8p_impl.h): compile-time bits of the kernel instantiations, OR-ed
+// together by the host selection (gemm8p.hip); anything else stays on the older kernels
+// ---------------------------------------------------------------------------------------------
+constexpr int E_RES = 1;        // + residual (same shape / type as C)
+constexpr int E_GELU = 2;       // exact-erf GELU, pre-activation saved to p.preact when non-null
+constexpr int E_GELUGRAD = 4;   // multiply by GELU'(p.preact)
+constexpr int E_CSTATS = 8;     // per-column sum / sum of squares of the accumulators -> p.colstats (conv forward)
+constexpr int E_RELUMASK = 16;  // C = relu_src > 0 ? value : 0 (after the residual)
+constexpr int E_BNB1 = 32;      // BatchNorm-backward sums against bnb_x[0]
+constexpr int E_BNB2 = 64;      // ... and bnb_x[1]
+constexpr int E_F32 = 128;      // float32 C, plain stores (slab or final), alpha / bias only
+constexpr int E_SCALE_RELU = 256;  // eval-mode BatchNorm folded in: per-column scale (+ bias = shift) and ReLU last (act == 3)
 
 template <typename T>
 struct ET;

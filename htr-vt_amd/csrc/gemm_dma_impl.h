@@ -24,30 +24,7 @@ using namespace htrvt;
 namespace {
 
 constexpr int BK = 64;
-constexpr unsigned OOB = 0x80000000u;
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
-// One LDS-DMA piece: 64 lanes x 16 B -> LDS [lds_addr, lds_addr + 1 KiB).  Inline asm on purpose: hipcc would
-// otherwise order every later ds_read behind the DMA with s_waitcnt vmcnt(0) (it cannot prove the two LDS stages
-// disjoint), which serialises load and MFMA.  The kernel counts these loads itself (vmcnt before the barrier).
-__device__ __forceinline__ void dma16(const i32x4_t& rsrc, unsigned lds_addr, unsigned voff) {
-  unsigned keep;
-  asm volatile(
-      "s_nop 4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(lds_addr), "s"(rsrc)
-      : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr_of(const char* p) {
-  return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const char*)p;
-}
+// dma16, lds_addr_of, make_rsrc, OOB: gemm_common.h
 
 // Split factors that are not multiples of 8 (layer 2: 14 ranges x 18 tiles, layer 3: 7 x 72, layer 1: 42 x 6): workgroup b runs on
 // XCD b % 8, so the workgroups of XCD x are b = x, x + 8, ...; give them CONSECUTIVE (range, tile) pairs -- XCD x holds the linear
@@ -120,8 +97,7 @@ struct DmaLoader {
   template <class P>
   __device__ __forceinline__ void init(const P& p, const char* base, long long ld, int row0, int rows_total, int wave,
                                        int lane) {
-    const unsigned long long ba = (unsigned long long)base;  // raw buffer, stride 0, 2 GiB of records
-    rsrc = i32x4_t{(int)(unsigned)(ba & 0xffffffffull), (int)(unsigned)((ba >> 32) & 0xffffull), (int)OOB, 0x00020000};
+    rsrc = make_rsrc(base);
     ld2 = (unsigned)(ld * 2);
     cur_ti = -1;
 #pragma unroll
