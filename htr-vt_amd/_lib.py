@@ -140,6 +140,9 @@ PROTOTYPES = {
     "htrvt_attn_local_supported": (i32, [i32, i32, i32]),
     "htrvt_attn_local_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
     "htrvt_attn_local_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "htrvt_attn_local_shift_supported": (i32, [i32, i32, i32, i32]),
+    "htrvt_attn_local_shift_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "htrvt_attn_local_shift_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "htrvt_lgp_pool_norm_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "htrvt_lgp_pool_norm_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "htrvt_lgp_upsample_fwd": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),

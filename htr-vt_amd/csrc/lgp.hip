@@ -6,6 +6,9 @@
 //                                queries DO attend to; the kernels build those rows from the bias and return their k / v
 //                                gradient per image.  Scores never leave the chip and nothing but qkv is saved: the backward
 //                                recomputes the (at most 16 x 16) softmax.
+//   htrvt_attn_local_shift_*     the same kernels with the Swin-style shift of the SGM local-global fork's WindowMHSA1D
+//                                (model_sgm_localglobal/model/HTR_VT.py:118-152: roll, pad, attend, crop, roll back) as
+//                                index arithmetic on the token a window slot reads and writes; no mask across the wrap.
 //   htrvt_lgp_pool_norm_fwd/bwd  PooledGlobalMHSA (:47-60) up to its qkv Linear: adaptive_avg_pool1d over the tokens fused
 //                                with the affine-free LayerNorm of each pooled token.  Backward by gather (a token collects from
 //                                the one or two bins that contain it), added onto the gradient that is already there.
@@ -115,7 +118,11 @@ struct LocalUnit {
   bool rowact, real;
 };
 
-__device__ __forceinline__ LocalUnit local_unit(long long u, long long units, int N, int heads, int w, int nW, int lane) {
+// Shifted windows (WindowMHSA1D with shift s: roll the tokens by s, pad, attend, crop, roll back) are index arithmetic: token j
+// sits in rolled slot (j + s) mod N, window t holds slots [t w, t w + w), slots >= N of the last window are the padding rows,
+// and slot p < N reads and writes token (p - s) mod N.  `shift` arrives reduced mod N, so that is one compare and one add.
+__device__ __forceinline__ LocalUnit local_unit(long long u, long long units, int N, int heads, int w, int nW, int shift,
+                                                int lane) {
   LocalUnit x;
   const bool valid = u < units;
   const long long uu = valid ? u : 0;
@@ -124,8 +131,9 @@ __device__ __forceinline__ LocalUnit local_unit(long long u, long long units, in
   x.b = (int)(uu / ((long long)heads * nW));
   x.r = lane >> 2;
   x.p = lane & 3;
-  x.tok = win * w + x.r;
-  const int left = N - win * w;            // real tokens of this window
+  const int slot = win * w + x.r;
+  x.tok = slot - shift + (slot < shift ? N : 0);
+  const int left = N - win * w;            // real slots of this window
   x.nvalid = left < w ? left : w;
   x.rowact = valid && x.r < w;
   x.real = x.rowact && x.r < x.nvalid;
@@ -135,13 +143,13 @@ __device__ __forceinline__ LocalUnit local_unit(long long u, long long units, in
 template <typename T, int HD, int WPB>
 __global__ __launch_bounds__(64 * WPB) void attn_local_fwd_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
                                                                   T* __restrict__ out, int N, int heads, int w, int nW,
-                                                                  float scale, long long units) {
+                                                                  int shift, float scale, long long units) {
   using G = LocalGeom<T, HD>;
   using V = typename G::V;
   using Raw = typename G::Raw;
   __shared__ Raw lds[WPB][2][G::MAT];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, lane);
+  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, shift, lane);
   const int D = heads * HD;
   Raw* kl = lds[wv][0];
   Raw* vl = lds[wv][1];
@@ -231,14 +239,14 @@ template <typename T, int HD, int WPB>
 __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
                                                                   const T* __restrict__ dout, T* __restrict__ dqkv,
                                                                   float* __restrict__ dpad, int N, int heads, int w, int nW,
-                                                                  float scale, long long units) {
+                                                                  int shift, float scale, long long units) {
   using G = LocalGeom<T, HD>;
   using V = typename G::V;
   using Raw = typename G::Raw;
   __shared__ Raw lds[WPB][4][G::MAT];
   __shared__ float coef[WPB][2][WMAX][WMAX + 1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, lane);
+  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, shift, lane);
   const int D = heads * HD;
   Raw* ql = lds[wv][0];
   Raw* kl = lds[wv][1];
@@ -672,58 +680,97 @@ extern "C" int htrvt_attn_local_supported(int hd, int window, int dtype) {
   return local_check("htrvt_attn_local", 0, 1, 1, hd, window, dtype) == 0 ? 1 : 0;
 }
 
+static int shift_check(const char* who, int window, int shift) {
+  HTRVT_REQUIRE(shift >= 0 && shift < window, "%s: shift=%d outside 0 ... window - 1 = %d", who, shift, window - 1);
+  return 0;
+}
+
+extern "C" int htrvt_attn_local_shift_supported(int hd, int window, int shift, int dtype) {
+  if (local_check("htrvt_attn_local_shift", 0, 1, 1, hd, window, dtype)) return 0;
+  return shift_check("htrvt_attn_local_shift", window, shift) == 0 ? 1 : 0;
+}
+
 #define LOCAL_LAUNCH(KERNEL, T, HD, WPB, ...)                                                                   \
   hipLaunchKernelGGL((KERNEL<T, HD, WPB>), dim3((unsigned)((units + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, __VA_ARGS__)
 
-extern "C" int htrvt_attn_local_fwd(const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd,
-                                    int window, float scale, int dtype, void* stream) {
-  if (local_check("htrvt_attn_local_fwd", B, N, heads, hd, window, dtype)) return -1;
-  HTRVT_REQUIRE(qkv && qkv_bias && out, "htrvt_attn_local_fwd: null buffer");
-  HTRVT_REQUIRE(!misaligned16(qkv, out), "htrvt_attn_local_fwd: qkv / out must be 16-byte aligned");
+// the two entry points of each direction share one launch; `shift` is checked by the caller and reduced mod N here
+static int local_fwd(const char* who, const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd,
+                     int window, int shift, float scale, int dtype, void* stream) {
+  if (local_check(who, B, N, heads, hd, window, dtype)) return -1;
+  HTRVT_REQUIRE(qkv && qkv_bias && out, "%s: null buffer", who);
+  HTRVT_REQUIRE(!misaligned16(qkv, out), "%s: qkv / out must be 16-byte aligned", who);
   const int nW = (N + window - 1) / window;
   const long long units = (long long)B * nW * heads;
   if (units == 0) return 0;
-  HTRVT_REQUIRE(units < (1ll << 31), "htrvt_attn_local_fwd: too many windows");
+  HTRVT_REQUIRE(units < (1ll << 31), "%s: too many windows", who);
   hipStream_t st = (hipStream_t)stream;
+  const int sh = shift % N;
   if (dtype == HTRVT_BF16) {
     if (hd == 128)
-      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 128, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 128, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, sh, scale, units);
     else
-      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, sh, scale, units);
   } else {
     if (hd == 128)
-      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 128, 2, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 128, 2, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, sh, scale, units);
     else
-      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 64, 4, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 64, 4, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, sh, scale, units);
   }
   return check_launch("attn_local_fwd");
 }
 
-extern "C" int htrvt_attn_local_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B,
-                                    int N, int heads, int hd, int window, float scale, int dtype, void* stream) {
-  if (local_check("htrvt_attn_local_bwd", B, N, heads, hd, window, dtype)) return -1;
-  HTRVT_REQUIRE(qkv && qkv_bias && dout && dqkv && dpad, "htrvt_attn_local_bwd: null buffer");
-  HTRVT_REQUIRE(!misaligned16(qkv, dout, dqkv), "htrvt_attn_local_bwd: qkv / dout / dqkv must be 16-byte aligned");
+static int local_bwd(const char* who, const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B,
+                     int N, int heads, int hd, int window, int shift, float scale, int dtype, void* stream) {
+  if (local_check(who, B, N, heads, hd, window, dtype)) return -1;
+  HTRVT_REQUIRE(qkv && qkv_bias && dout && dqkv && dpad, "%s: null buffer", who);
+  HTRVT_REQUIRE(!misaligned16(qkv, dout, dqkv), "%s: qkv / dout / dqkv must be 16-byte aligned", who);
   const int nW = (N + window - 1) / window;
   const long long units = (long long)B * nW * heads;
   if (units == 0) return 0;
-  HTRVT_REQUIRE(units < (1ll << 31), "htrvt_attn_local_bwd: too many windows");
+  HTRVT_REQUIRE(units < (1ll << 31), "%s: too many windows", who);
   hipStream_t st = (hipStream_t)stream;
   if (N % window == 0)      // no padding keys: their gradient is zero
     HTRVT_REQUIRE(hipMemsetAsync(dpad, 0, sizeof(float) * 2 * (size_t)B * heads * hd, st) == hipSuccess,
-                  "htrvt_attn_local_bwd: clearing dpad failed");
+                  "%s: clearing dpad failed", who);
+  const int sh = shift % N;
   if (dtype == HTRVT_BF16) {
     if (hd == 128)
-      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 128, 2, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 128, 2, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
     else
-      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
   } else {
     if (hd == 128)
-      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 128, 1, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 128, 1, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
     else
-      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 64, 2, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, scale, units);
+      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 64, 2, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
   }
   return check_launch("attn_local_bwd");
+}
+
+extern "C" int htrvt_attn_local_fwd(const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd,
+                                    int window, float scale, int dtype, void* stream) {
+  return local_fwd("htrvt_attn_local_fwd", qkv, qkv_bias, out, B, N, heads, hd, window, 0, scale, dtype, stream);
+}
+
+extern "C" int htrvt_attn_local_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B,
+                                    int N, int heads, int hd, int window, float scale, int dtype, void* stream) {
+  return local_bwd("htrvt_attn_local_bwd", qkv, qkv_bias, dout, dqkv, dpad, B, N, heads, hd, window, 0, scale, dtype, stream);
+}
+
+extern "C" int htrvt_attn_local_shift_fwd(const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd,
+                                          int window, int shift, float scale, int dtype, void* stream) {
+  if (local_check("htrvt_attn_local_shift_fwd", B, N, heads, hd, window, dtype)) return -1;
+  if (shift_check("htrvt_attn_local_shift_fwd", window, shift)) return -1;
+  return local_fwd("htrvt_attn_local_shift_fwd", qkv, qkv_bias, out, B, N, heads, hd, window, shift, scale, dtype, stream);
+}
+
+extern "C" int htrvt_attn_local_shift_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad,
+                                          int B, int N, int heads, int hd, int window, int shift, float scale, int dtype,
+                                          void* stream) {
+  if (local_check("htrvt_attn_local_shift_bwd", B, N, heads, hd, window, dtype)) return -1;
+  if (shift_check("htrvt_attn_local_shift_bwd", window, shift)) return -1;
+  return local_bwd("htrvt_attn_local_shift_bwd", qkv, qkv_bias, dout, dqkv, dpad, B, N, heads, hd, window, shift, scale, dtype,
+                   stream);
 }
 
 extern "C" int htrvt_lgp_pool_norm_fwd(const void* x, void* z, float* mean, float* rstd, int B, int N, int G, int D, float eps,

@@ -44,7 +44,8 @@ class ModelShape:
     """Static shape of one model (mirrors MaskedAutoencoderViT.__init__, HTR_VT.py:143-172)."""
 
     def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS,
-                 pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False, lgp=None, pos_table=None):
+                 pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False, lgp=None, pos_table=None,
+                 local=None):
         """The switches of the window-attention fork (model_window/model/HTR_VT.py), defaults = model_v1:
         pos_embed: tokens get the absolute position embedding; whiten_logits: the parameter-free LayerNorm over the logits;
         relpos: None, or per block (window, shift) -- attention with the block's relative-position table
@@ -54,7 +55,12 @@ class ModelShape:
         lgp: (window, g_tokens, branch_eps) -- every block is a LocalGlobalParallelBlockSimple: window attention over
         `window` tokens beside attention over min(g_tokens, N) pooled tokens (their LayerNorm without affine at branch_eps),
         fused by a Linear(2D, D); pos_table: float32 [N, D] position embedding the model supplies (the fork keeps it in a
-        non-persistent buffer, so no state dict carries it); the token count is what the stem leaves, as for relpos."""
+        non-persistent buffer, so no state dict carries it); the token count is what the stem leaves, as for relpos.
+        The SGM local-global fork (model_sgm_localglobal/model/HTR_VT.py), default None:
+        local: per block None (the v1 full-attention block) or (window, shift) -- a LocalBlock1D: the v1 block with its
+        attention inside windows of `window` tokens rolled by `shift` (csrc/lgp.hip; padding slots = the qkv bias, no mask
+        across the wrap).  v1 parameter names and the v1 position table `pos_embed`, whose num_patches rows must be the
+        tokens the stem leaves (any W that is a multiple of 8 for which the two agree)."""
         self.nb_cls = int(nb_cls)
         self.pos_embed, self.whiten_logits, self.dropout = bool(pos_embed), bool(whiten_logits), bool(dropout)
         self.relpos = None if relpos is None else [None if g is None else (int(g[0]), int(g[1])) for g in relpos]
@@ -67,8 +73,18 @@ class ModelShape:
         self.num_patches = self.grid[0] * self.grid[1]
         assert self.D % 32 == 0 and self.D % self.heads == 0
         self.lgp = None if lgp is None else (int(lgp[0]), int(lgp[1]), float(lgp[2]))
+        self.local = None if local is None else [None if g is None else (int(g[0]), int(g[1])) for g in local]
         self.pos_table = pos_table
-        if self.lgp is not None:
+        if self.local is not None:
+            if self.relpos is not None or self.lgp is not None:
+                raise ValueError("ModelShape: `local` excludes `relpos` and `lgp` (one kind of block list per model)")
+            assert len(self.local) == self.depth and self.pos_embed and pos_table is None
+            assert all(g is None or 0 <= g[1] < g[0] for g in self.local), "local: 0 <= shift < window"
+            assert self.H % 64 == 0 and self.W % 8 == 0, "img_size: H a multiple of 64, W of 8"
+            if self.num_patches != stem_tokens(self.H, self.W):
+                raise ValueError(f"img_size {self.H} x {self.W} / patch_size {tuple(patch_size)}: the position table has "
+                                 f"{self.num_patches} rows, the stem leaves {stem_tokens(self.H, self.W)} tokens")
+        elif self.lgp is not None:
             assert self.relpos is None and pos_table is not None
             assert self.H % 64 == 0 and self.W % 8 == 0, "img_size: H a multiple of 64, W of 8"
             self.num_patches = stem_tokens(self.H, self.W)
@@ -126,6 +142,9 @@ class Engine:
         assert not self.split or dtype == torch.float32, "split_bf16 is a mode of the float32 path"
         if self.split and shape.lgp is not None:
             raise NotImplementedError("split_bf16 is not served for the LGP blocks: use torch.float32 (parity) or torch.bfloat16")
+        if self.split and shape.local is not None:
+            raise NotImplementedError("split_bf16 is not served for local window blocks: use torch.float32 (parity) or "
+                                      "torch.bfloat16")
         self.gdt = torch.bfloat16 if self.split else dtype
         self._split_cache = []       # backward: the few most recent (source tensor, cat, hi, lo) splits (a gradient feeds dgrad AND wgrad)
         self._saved_planes, self._saving = {}, False    # forward(save=True): id(activation) -> its hi / lo planes, for the weight gradients
@@ -1072,15 +1091,18 @@ class Engine:
             wq, _ = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             qkv = self.linear_fwd(ln1, wq, P[p + ".attn.qkv.bias"])
             geo = s.relpos[i] if s.relpos is not None else None
+            loc = s.local[i] if s.local is not None else None
             if geo is not None:
                 O, Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, B, N, save)
+            elif loc is not None:   # LocalBlock1D: nothing but qkv and O is kept, the backward recomputes the windows' softmax
+                O, Pm, lse = seq_ops.local_attention_fwd(qkv, P[p + ".attn.qkv.bias"], B, N, s.heads, *loc), None, None
             else:
                 O, Pm, lse = self._attention_fwd(qkv, B, N, save)
             wp, _ = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             x1 = self.linear_fwd(O, wp, P[p + ".attn.proj.bias"], residual=xt)
             x2, mlp = self._mlp_fwd(P, p, x1, save)
             if save:
-                enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, geo=geo, **mlp))
+                enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, geo=geo, loc=loc, **mlp))
             xt = x2
 
         # --- norm + head + sequence LayerNorm (HTR_VT.py:236-239) ---
@@ -1321,13 +1343,19 @@ class Engine:
             wp, wpt = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
             dO = self.linear_dgrad(dx1, wp, wpt)
             self.linear_wgrad(dx1, e["O"], G[p + ".attn.proj.weight"], G[p + ".attn.proj.bias"])
+            dpad = None
             if e.get("geo") is not None:
                 dqkv = self._relpos_attention_bwd(P, G, e, dO, B, N)
+            elif e.get("loc") is not None:
+                dqkv, dpad = seq_ops.local_attention_bwd(e["qkv"], P[p + ".attn.qkv.bias"], dO, B, N, s.heads, *e["loc"])
             else:
                 dqkv = self._attention_bwd(e["qkv"], e["P"], e["lse"], e["O"], dO, B, N)
             wq, wqt = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
             dln1 = self.linear_dgrad(dqkv, wq, wqt)
-            self.linear_wgrad(dqkv, e["ln1"], G[p + ".attn.qkv.weight"], G[p + ".attn.qkv.bias"])
+            gqb = G[p + ".attn.qkv.bias"]
+            self.linear_wgrad(dqkv, e["ln1"], G[p + ".attn.qkv.weight"], gqb)
+            if dpad is not None and N % e["loc"][0]:    # the padding rows' k / v gradient, as in _lgp_block_bwd
+                self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, gqb.data_ptr() + 4 * D, dti=0), dpad)
             dx = self.ln_bwd(dln1, e["x0"], e["m1"], e["r1"], P[p + ".norm1.weight"], dx1, G[p + ".norm1.weight"],
                              G[p + ".norm1.bias"])
 

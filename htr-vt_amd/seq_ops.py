@@ -212,24 +212,24 @@ def cross_attention_bwd(Q, KV, P, dout):
 
 # ---- LGP fork (csrc/lgp.hip): window-12 attention, pool + LayerNorm, up-sample * sigmoid(alpha) -------------------------
 
-def local_attention_fwd(qkv, qkv_bias, B, N, h, window):
+def local_attention_fwd(qkv, qkv_bias, B, N, h, window, shift=0):
     """attention inside windows of `window` tokens; the padding slots of a ragged last window are rows equal to the qkv
-    Linear's float32 bias"""
+    Linear's float32 bias.  shift (0 ... window - 1): the windows are those of the tokens rolled by `shift`"""
     D, hd = _heads(qkv, h)
     out = _like(qkv, B * N, D)
-    check(lib.htrvt_attn_local_fwd(ptr(qkv), ptr(qkv_bias), ptr(out), B, N, h, hd, window, hd ** -0.5, dt(qkv.dtype), stream()),
-          "attn_local_fwd")
+    check(lib.htrvt_attn_local_shift_fwd(ptr(qkv), ptr(qkv_bias), ptr(out), B, N, h, hd, window, shift, hd ** -0.5,
+                                         dt(qkv.dtype), stream()), "attn_local_shift_fwd")
     return out
 
 
-def local_attention_bwd(qkv, qkv_bias, dout, B, N, h, window):
+def local_attention_bwd(qkv, qkv_bias, dout, B, N, h, window, shift=0):
     """(dqkv, dpad float32 [B, 2*D]: per image the gradient of the padding rows' k / v, meaningful where N % window; its
     column sum belongs to the k / v thirds of the bias gradient)"""
     D, hd = _heads(qkv, h)
     dqkv = torch.empty_like(qkv)
     dpad = _f32(qkv, B, 2 * D)
-    check(lib.htrvt_attn_local_bwd(ptr(qkv), ptr(qkv_bias), ptr(dout), ptr(dqkv), ptr(dpad), B, N, h, hd, window, hd ** -0.5,
-                                   dt(qkv.dtype), stream()), "attn_local_bwd")
+    check(lib.htrvt_attn_local_shift_bwd(ptr(qkv), ptr(qkv_bias), ptr(dout), ptr(dqkv), ptr(dpad), B, N, h, hd, window, shift,
+                                         hd ** -0.5, dt(qkv.dtype), stream()), "attn_local_shift_bwd")
     return dqkv, dpad
 
 

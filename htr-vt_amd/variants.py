@@ -195,17 +195,17 @@ class _LocalWindowAttention(torch.autograd.Function):
     equal to it, which real queries attend to; its k / v thirds get the gradient of those rows."""
 
     @staticmethod
-    def forward(ctx, qkv, qkv_bias, B, N, heads, window):
+    def forward(ctx, qkv, qkv_bias, B, N, heads, window, shift):
         if qkv_bias.dtype != torch.float32:
             raise TypeError(f"qkv bias: float32 expected (the parameter as stored), got {qkv_bias.dtype}")
         qkv, qkv_bias = qkv.contiguous(), qkv_bias.contiguous()
         ctx.save_for_backward(qkv, qkv_bias)
-        ctx.dims = (B, N, heads, window)
+        ctx.dims = (B, N, heads, window, shift)
         return seq_ops.local_attention_fwd(qkv, qkv_bias, *ctx.dims)
 
     @staticmethod
     def backward(ctx, dout):
-        B, N, _, window = ctx.dims
+        B, N, _, window, _ = ctx.dims
         qkv, qkv_bias = ctx.saved_tensors
         D = qkv.shape[1] // 3
         dqkv, dpad = seq_ops.local_attention_bwd(qkv, qkv_bias, dout.contiguous().to(qkv.dtype), *ctx.dims)
@@ -214,20 +214,22 @@ class _LocalWindowAttention(torch.autograd.Function):
             dbias = torch.zeros_like(qkv_bias)
             if N % window:
                 colsum(dpad, B, 2 * D, 2 * D, dbias.data_ptr() + 4 * D, dti=dt(torch.float32))
-        return dqkv, dbias, None, None, None, None
+        return dqkv, dbias, None, None, None, None, None
 
 
-def local_attention_supported(head_dim, window, dtype):
-    return bool(lib.htrvt_attn_local_supported(head_dim, window, dt(dtype)))
+def local_attention_supported(head_dim, window, dtype, shift=0):
+    return bool(lib.htrvt_attn_local_shift_supported(head_dim, window, shift, dt(dtype)))
 
 
-def local_window_attention(qkv, qkv_bias, B, N, heads, window):
-    """WindowMHSA1D of the LGP fork on its qkv Linear's output: attention inside non-overlapping windows of `window` tokens,
-    the padding slots of a ragged last window being rows equal to `qkv_bias` (not masked).  Differentiable in both."""
+def local_window_attention(qkv, qkv_bias, B, N, heads, window, shift=0):
+    """WindowMHSA1D of the LGP and SGM local-global forks on its qkv Linear's output: attention inside non-overlapping
+    windows of `window` tokens, the padding slots of a ragged last window being rows equal to `qkv_bias` (not masked).
+    shift (0 ... window - 1): the windows of the tokens rolled by `shift`, as torch.roll(x, shift, 1) in front of the
+    padding and the roll back behind the crop give them; no mask across the wrap.  Differentiable in qkv and the bias."""
     _need_device(qkv, qkv_bias)
-    if not local_attention_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype):
+    if not local_attention_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype, shift):
         raise ValueError(f"window attention: {lib.htrvt_last_error().decode()}")
-    return _LocalWindowAttention.apply(qkv, qkv_bias, B, N, heads, window)
+    return _LocalWindowAttention.apply(qkv, qkv_bias, B, N, heads, window, shift)
 
 
 class _PoolNorm(torch.autograd.Function):

@@ -488,6 +488,13 @@ int htrvt_sgm_convert(const void* src, int src_dtype, void* dst, int dst_dtype, 
  *   _bwd: dqkv [B N][3][heads][hd] written whole; dpad float32 [B][2][heads hd] overwritten with the summed gradient of each
  *   image's padding rows' k and v (zeros when N % window == 0) -- a column sum over B adds it to d qkv.bias[D : 3D].
  *   _supported: 1 if (hd, window, dtype) is served, else 0 with the reason in htrvt_last_error().
+ * htrvt_attn_local_shift_*: the same kernels and argument contract with the Swin-style `shift` of WindowMHSA1D (0 <= shift <
+ *   window, refused otherwise; shift 0 is bitwise htrvt_attn_local_*): the reference rolls the tokens by `shift` before it
+ *   pads and rolls the cropped output back.  Here that is index arithmetic on the same [B N] buffers: token j sits in rolled
+ *   slot p = (j + shift) mod N, window t holds slots [t window, (t + 1) window), slots p >= N of the last window are the
+ *   padding rows (k = v = qkv_bias), and slot p < N reads qkv and writes out / dqkv at token (p - shift) mod N.  So window 0
+ *   mixes the last `shift` tokens of the line with its first window - shift (no mask across the wrap), and the ragged window
+ *   holds tokens N - shift - N % window ... N - shift - 1.  dpad as above.
  * htrvt_lgp_pool_norm_fwd: z [B G][D] = LayerNorm without affine (eps) of adaptive_avg_pool1d(x [B N][D]) along the tokens,
  *   bin g = tokens [floor(g N / G), ceil((g + 1) N / G)); mean / rstd float32 [B G].  1 <= G <= N, D <= 2048.
  *   _bwd: dx [B N][D] = (accumulate: +=) the gradient of x for dz, each token gathering from the bins that contain it;
@@ -501,6 +508,11 @@ int htrvt_attn_local_fwd(const void* qkv, const float* qkv_bias, void* out, int 
                          float scale, int dtype, void* stream);
 int htrvt_attn_local_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B, int N,
                          int heads, int hd, int window, float scale, int dtype, void* stream);
+int htrvt_attn_local_shift_supported(int hd, int window, int shift, int dtype);
+int htrvt_attn_local_shift_fwd(const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd, int window,
+                               int shift, float scale, int dtype, void* stream);
+int htrvt_attn_local_shift_bwd(const void* qkv, const float* qkv_bias, const void* dout, void* dqkv, float* dpad, int B, int N,
+                               int heads, int hd, int window, int shift, float scale, int dtype, void* stream);
 int htrvt_lgp_pool_norm_fwd(const void* x, void* z, float* mean, float* rstd, int B, int N, int G, int D, float eps, int dtype,
                             void* stream);
 int htrvt_lgp_pool_norm_bwd(const void* dz, const void* z, const float* rstd, float* workspace, void* dx, int B, int N, int G,
