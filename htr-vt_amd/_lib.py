@@ -148,6 +148,15 @@ PROTOTYPES = {
     "htrvt_lgp_upsample_fwd": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
     "htrvt_lgp_upsample_bwd_workspace_floats": (i64, [i32, i32]),
     "htrvt_lgp_upsample_bwd": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_mixer_rows": (i32, [i32, i32, i32, i32]),
+    "htrvt_mixer_fwd_workspace_floats": (i64, [i32, i32, i32, i32]),
+    "htrvt_mixer_bwd_workspace_floats": (i64, [i32, i32, i32, i32, i32]),
+    "htrvt_mixer_reduce_rows": (i32, [i64, i32, i32]),
+    "htrvt_mixer_fwd_train": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_mixer_bn_silu": (i32, [vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_mixer_fwd_eval": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_mixer_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_mixer_bwd": (i32, [vp] * 10 + [i32, i32, i32, i32, i32, vp]),
 }
 
 

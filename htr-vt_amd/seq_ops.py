@@ -1,9 +1,9 @@
-"""The launch sequences of the attention flavours and norms, each written once.
+"""The launch sequences of the attention flavours, norms and the convolutional token mixer, each written once.
 
 Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
 torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
-here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, and the autograd wrappers of variants.py.
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, and the autograd wrappers of variants.py.
 
 Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5."""
 import torch
@@ -18,6 +18,24 @@ def _f32(x, *shape):
 
 def _like(x, *shape):
     return torch.empty(*shape, dtype=x.dtype, device=x.device)
+
+
+def convert(src, dst, accumulate=False):
+    """dst (+)= src between float32 / bfloat16 buffers of equal size"""
+    check(lib.htrvt_sgm_convert(ptr(src), dt(src.dtype), ptr(dst), dt(dst.dtype), src.numel(), int(accumulate), stream()),
+          "sgm_convert")
+    return dst
+
+
+def linear_wgrad(dy, x, rows):
+    """a Linear's parameter gradients: dW [N, K] float32 = dy[rows, N]^T x[rows, K]; db [N] = column sums of dy"""
+    N, K = dy.shape[1], x.shape[1]
+    dw = torch.zeros(N, K, dtype=torch.float32, device=dy.device)
+    gemm(dy, x, dw, dtype=dy.dtype, M=N, N=K, K=rows, lda=N, ldb=K, ldc=K, a_layout=MNMAJOR, b_layout=MNMAJOR,
+         accumulate=True, c_f32=True)
+    db = torch.zeros(N, dtype=torch.float32, device=dy.device)
+    colsum(dy, rows, N, N, db, dti=dt(dy.dtype))
+    return dw, db
 
 
 def _heads(qkv, h):
@@ -274,3 +292,78 @@ def upsample_bwd(dout, y, logit_alpha, dalpha, B, N, G):
     check(lib.htrvt_lgp_upsample_bwd(ptr(dout), dout.stride(0), ptr(y), ptr(logit_alpha), ptr(dy), ptr(dalpha), ptr(ws), B, N, G,
                                      D, dt(y.dtype), stream()), "lgp_upsample_bwd")
     return dy
+
+
+# ---- macaron forks (csrc/mixer.hip): GLU -> depthwise token conv -> BatchNorm1d -> SiLU between the mixer's Linear layers
+
+def conv_mixer_fwd(u, weight, B, N, bn=None, training=False, eps=1e-5, momentum=0.1, conv_bias=None, save=True):
+    """u [B*N, 2*D] (pw_in's output), weight float32 [D, 1, k] -> (s [B*N, D], saved).  bn: None (use_bn=False: z = c +
+    conv_bias) or (gamma, beta, running_mean, running_var, num_batches_tracked); in training mode the batch statistics
+    are used and the three buffers updated in place, else the running ones.  saved = (c, scale, shift, mean, rstd) for
+    conv_mixer_bwd: c [B*N, D] is the convolution's output (None without `save` outside training), the rest float32 [D]
+    or None."""
+    D, k, dti, st = u.shape[1] // 2, weight.shape[-1], dt(u.dtype), stream()
+    s = _like(u, B * N, D)
+    if bn is None:
+        c = _like(u, B * N, D) if save else None
+        check(lib.htrvt_mixer_fwd_eval(ptr(u), ptr(weight), None, ptr(conv_bias), ptr(c), ptr(s), B, N, D, k, dti, st),
+              "mixer_fwd_eval")
+        return s, (c, None, conv_bias, None, None)
+    gamma, beta, rmean, rvar, nbt = bn
+    scale, shift, rstd = _f32(u, D), _f32(u, D), _f32(u, D)
+    if not training:
+        c = _like(u, B * N, D) if save else None
+        check(lib.htrvt_bn_eval_coeffs(ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), eps, ptr(scale), ptr(shift), ptr(rstd),
+                                       D, st), "bn_eval_coeffs")
+        check(lib.htrvt_mixer_fwd_eval(ptr(u), ptr(weight), ptr(scale), ptr(shift), ptr(c), ptr(s), B, N, D, k, dti, st),
+              "mixer_fwd_eval")
+        return s, (c, scale, shift, rmean.clone() if save else None, rstd)
+    nws = lib.htrvt_mixer_fwd_workspace_floats(B, N, D, dti)
+    if nws < 0:
+        check(-1, "mixer_fwd_train")
+    c, partial, mean = _like(u, B * N, D), _f32(u, nws), _f32(u, D)
+    check(lib.htrvt_mixer_fwd_train(ptr(u), ptr(weight), ptr(c), ptr(partial), B, N, D, k, dti, st), "mixer_fwd_train")
+    check(lib.htrvt_bn_finalize(ptr(partial), lib.htrvt_mixer_rows(B, N, D, dti), D, float(B * N), ptr(gamma), ptr(beta), eps,
+                                momentum, ptr(rmean), ptr(rvar), ptr(nbt), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), st),
+          "bn_finalize")
+    conv_mixer_act(c, scale, shift, s)
+    return s, (c, scale, shift, mean, rstd)
+
+
+def conv_mixer_act(c, scale, shift, s=None):
+    """s = silu(c * scale + shift): the train forward's second pass, and the backward's way to s without keeping it"""
+    s = torch.empty_like(c) if s is None else s
+    check(lib.htrvt_mixer_bn_silu(ptr(c), ptr(scale), ptr(shift), ptr(s), c.shape[0], c.shape[1], dt(c.dtype), stream()),
+          "mixer_bn_silu")
+    return s
+
+
+def conv_mixer_bwd(ds, u, weight, B, N, saved, gamma=None, training=False, need_bias=False):
+    """ds [B*N, D] -> (du [B*N, 2*D], dweight [D, 1, k], dgamma, dbeta, dbias), float32 parameter gradients; dgamma / dbeta
+    are None without BatchNorm (gamma None), dbias is None unless need_bias"""
+    c, scale, shift, mean, rstd = saved
+    D, k, dti, st = u.shape[1] // 2, weight.shape[-1], dt(u.dtype), stream()
+    dgamma = dbeta = coef = None
+    if gamma is not None:
+        nred = lib.htrvt_mixer_reduce_rows(B * N, D, dti)
+        partial, coef = _f32(u, nred, 2, D), _f32(u, 3, D)
+        check(lib.htrvt_mixer_bwd_reduce(ptr(ds), ptr(c), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), ptr(partial), B * N, D,
+                                         dti, st), "mixer_bwd_reduce")
+        dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+        check(lib.htrvt_bn_bwd_finalize(ptr(partial), nred, D, float(B * N) if training else 0.0, ptr(gamma), ptr(mean),
+                                        ptr(rstd), ptr(dgamma), ptr(dbeta), ptr(coef), st), "bn_bwd_finalize")
+    rows = lib.htrvt_mixer_rows(B, N, D, dti)
+    if rows < 0:
+        check(-1, "mixer_bwd")
+    pw = _f32(u, rows, D * k)
+    pb = _f32(u, rows, D) if need_bias else None
+    du = torch.empty_like(u)
+    check(lib.htrvt_mixer_bwd(ptr(u), ptr(c), ptr(ds), ptr(weight), ptr(scale), ptr(shift), ptr(coef), ptr(du), ptr(pw), ptr(pb),
+                              B, N, D, k, dti, st), "mixer_bwd")
+    dweight = torch.zeros_like(weight)
+    colsum(pw, rows, D * k, D * k, dweight, dti=0)
+    dbias = None
+    if need_bias:
+        dbias = torch.zeros(D, dtype=torch.float32, device=u.device)
+        colsum(pb, rows, D, D, dbias, dti=0)
+    return du, dweight, dgamma, dbeta, dbias

@@ -23,7 +23,8 @@ import torch.nn as nn
 import htrvt_amd                        # noqa: F401  (loads libhtrvt_hip.so or raises)
 from htrvt_amd import seq_ops
 from htrvt_amd._lib import check, lib
-from htrvt_amd.ops import MNMAJOR, colsum, dt, gemm, ptr, stream
+from htrvt_amd.ops import MNMAJOR, dt, gemm, ptr, stream
+from htrvt_amd.seq_ops import convert as _convert, linear_wgrad as _wgrad
 
 SPECIAL_TOKENS = ("<pad>", "<eos>", "<bos_left>", "<bos_right>")
 
@@ -74,23 +75,6 @@ def make_context_batch(texts, stoi, sub_str_len=5, device='cuda'):
 
 def _empty(shape, dtype, dev):
     return torch.empty(shape, dtype=dtype, device=dev)
-
-
-def _convert(src, dst, accumulate=False):
-    check(lib.htrvt_sgm_convert(ptr(src), dt(src.dtype), ptr(dst), dt(dst.dtype), src.numel(), int(accumulate), stream()),
-          "sgm_convert")
-    return dst
-
-
-def _wgrad(dy, x, rows):
-    """dW [N, K] float32 = dy[rows, N]^T x[rows, K]; db [N] = column sums of dy"""
-    N, K = dy.shape[1], x.shape[1]
-    dw = torch.zeros(N, K, dtype=torch.float32, device=dy.device)
-    gemm(dy, x, dw, dtype=dy.dtype, M=N, N=K, K=rows, lda=N, ldb=K, ldc=K, a_layout=MNMAJOR, b_layout=MNMAJOR,
-         accumulate=True, c_f32=True)
-    db = torch.zeros(N, dtype=torch.float32, device=dy.device)
-    colsum(dy, rows, N, N, db, dti=dt(dy.dtype))
-    return dw, db
 
 
 PARAMS = ("emb.weight", "dir_left", "dir_right", "txt_proj.weight", "txt_proj.bias", "q_norm.weight", "q_norm.bias",

@@ -4,8 +4,8 @@ The models do not come through here.  The forks run as full drop-ins -- window/,
 and SGM head (sgm/model/sgm_head.py) call the same seq_ops functions directly, so an operator-level test of a wrapper
 below exercises the launch sequence the models run.  Wrapped: the window fork's relative-position attention (table
 -driven in bfloat16; in float32 ONE dense bias [heads, N, N], table entries inside a window and MASKED outside, into the
-batched-GEMM route), the SGM head's single-head cross-attention, and the LGP block's window-12 attention, pool + norm
-and scaled up-sampling.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
+batched-GEMM route), the SGM head's single-head cross-attention, the LGP block's window-12 attention, pool + norm
+and scaled up-sampling, and the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
 run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
 import torch
 
@@ -276,3 +276,47 @@ def upsample_scale(y, logit_alpha, B, G, N):
     times sigmoid(logit_alpha), logit_alpha a 0-dim float32 device tensor -> [B*N, D]"""
     _need_device(y, logit_alpha)
     return _UpsampleScale.apply(y, logit_alpha, B, G, N)
+
+
+# ---- macaron forks (model_sgm_macaron/model/HTR_VT.py ConvLocalMixer1D): the mixer between its Linear layers, csrc/mixer.hip
+
+class _GluDwconvBnSilu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, weight, bn_weight, bn_bias, conv_bias, running_mean, running_var, num_batches_tracked, B, N, training,
+                eps, momentum):
+        u, weight = u.contiguous(), weight.contiguous()
+        bn = None if bn_weight is None else (bn_weight.contiguous(), bn_bias.contiguous(), running_mean, running_var,
+                                             num_batches_tracked)
+        conv_bias = None if conv_bias is None else conv_bias.contiguous()
+        s, saved = seq_ops.conv_mixer_fwd(u, weight, B, N, bn=bn, training=training, eps=eps, momentum=momentum,
+                                          conv_bias=conv_bias)
+        ctx.save_for_backward(u, weight, None if bn is None else bn[0], *saved)
+        ctx.dims = (B, N, training)
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        u, weight, gamma, *saved = ctx.saved_tensors
+        B, N, training = ctx.dims
+        du, dweight, dgamma, dbeta, dbias = seq_ops.conv_mixer_bwd(
+            ds.contiguous().to(u.dtype), u, weight, B, N, saved, gamma=gamma, training=training,
+            need_bias=gamma is None and ctx.needs_input_grad[4])
+        return (du, dweight, dgamma, dbeta, dbias) + (None,) * 8
+
+
+def glu_dwconv_bn_silu(u, weight, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, B, N, training,
+                       eps=1e-5, momentum=0.1, conv_bias=None):
+    """ConvLocalMixer1D between pw_in and pw_out: u [B*N, 2*D] (float32 or bfloat16) -> silu(bn(dwconv(glu(u)))) [B*N, D].
+    weight: dwconv.weight float32 [D, 1, k], k odd <= 15, zero padding per image.  bn_weight / bn_bias float32 [D] with the
+    running buffers (training: batch statistics, the buffers updated in place; else the running statistics), or all None
+    for use_bn=False, where conv_bias (float32 [D] or None) is added instead.  D a multiple of 8.  Differentiable in u,
+    weight, bn_weight, bn_bias and conv_bias."""
+    tensors = [t for t in (u, weight, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, conv_bias)
+               if t is not None]
+    _need_device(*tensors)
+    if any(t.dtype != torch.float32 for t in tensors[1:] if t.is_floating_point()):
+        raise TypeError("glu_dwconv_bn_silu: float32 parameters and buffers expected (as stored)")
+    if (bn_weight is None) != (running_mean is None) or (bn_weight is not None and conv_bias is not None):
+        raise ValueError("glu_dwconv_bn_silu: either BatchNorm (weight, bias, running buffers) or a convolution bias")
+    return _GluDwconvBnSilu.apply(u, weight, bn_weight, bn_bias, conv_bias, running_mean, running_var, num_batches_tracked,
+                                  B, N, bool(training), float(eps), float(momentum))

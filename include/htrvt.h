@@ -523,6 +523,48 @@ int64_t htrvt_lgp_upsample_bwd_workspace_floats(int B, int G);
 int htrvt_lgp_upsample_bwd(const void* dout, int64_t ldd, const void* y, const float* logit_alpha, void* dy,
                            float* dlogit_alpha, float* workspace, int B, int N, int G, int D, int dtype, void* stream);
 
+/* ---- convolutional token mixer (model_sgm_macaron/model/HTR_VT.py:148-180, ConvLocalMixer1D) between its Linear layers:
+ * GLU -> depthwise Conv1d(k, padding k/2) along the tokens -> BatchNorm1d -> SiLU (csrc/mixer.hip).
+ * Layout: token rows as the GEMMs leave them, no transpose.  u [B*N][2D] (the pw_in output: value half, gate half),
+ * c / s / ds [B*N][D], du [B*N][2D], all of type dtype (float32 or bfloat16); w float32 [D][k] (dwconv.weight [D][1][k]);
+ * per-channel vectors (scale, shift, mean, rstd, coef) float32.  g = u[:, :D] * sigmoid(u[:, D:]) and
+ *   c[b][n][d] = sum_j w[d][j] * g[b][n + j - k/2][d],
+ * where a term whose token index leaves 0 .. N-1 of ITS OWN image b is zero (zero padding per image: no row of another
+ * image is read).  z = c * scale + shift, s = z * sigmoid(z); scale == NULL stands for 1 and shift == NULL for 0, so
+ * use_bn=False is scale = NULL, shift = dwconv.bias.  c is stored rounded to dtype, and z and the statistics are taken
+ * from the stored values.
+ * Refused (negative return, htrvt_last_error(), nothing launched): k even or outside 1 ... 15, D not a multiple of 8,
+ * u / c / s / ds / du not 16-byte aligned, B * N < 2 in htrvt_mixer_fwd_train.
+ * Workspaces (float32), all reductions being per-workgroup partial rows plus an ordered second stage (no float atomics):
+ *   htrvt_mixer_rows(B, N, D, dtype)                 partial rows R that fwd_train and bwd write for this shape
+ *   htrvt_mixer_fwd_workspace_floats(B, N, D, dtype) (R + 64) * 2 * D: partial [R][2][D] = (sum c, sum c^2) of fwd_train,
+ *       with the 64 scratch rows behind it that htrvt_bn_finalize(partial, R, D, count = B * N, ...) may use
+ *   htrvt_mixer_bwd_workspace_floats(B, N, D, k, dtype)  R * D * (k + 1): dw_partial [R][D * k] (+ db_partial [R][D])
+ *   htrvt_mixer_reduce_rows(rows, D, dtype)          partial rows Q of bwd_reduce: partial [Q][2][D]
+ * Forward, train: htrvt_mixer_fwd_train (c, partial) -> htrvt_bn_finalize -> htrvt_mixer_bn_silu (s).
+ * Forward, eval / no BatchNorm: htrvt_mixer_fwd_eval, one launch, coefficients from htrvt_bn_eval_coeffs; c may be NULL
+ *   when no backward follows.
+ * Backward: htrvt_mixer_bwd_reduce -> partial [Q][2][D] = (sum dz, sum dz * (c - mean) * rstd), dz = ds * silu'(z), for
+ *   htrvt_bn_bwd_finalize (mean == NULL: the second sum is zero); then htrvt_mixer_bwd: dc = coef[0] * dz + coef[1] * c +
+ *   coef[2] (coef [3][D] of htrvt_bn_bwd_finalize; NULL: dc = dz), dg = dc convolved with the flipped taps, du through the
+ *   GLU recomputed from u; dw_partial rows sum (htrvt_colsum over D * k columns) to d w [D][k], db_partial (may be NULL)
+ *   rows to d bias [D] = sum dc. */
+int htrvt_mixer_rows(int B, int N, int D, int dtype);
+int64_t htrvt_mixer_fwd_workspace_floats(int B, int N, int D, int dtype);
+int64_t htrvt_mixer_bwd_workspace_floats(int B, int N, int D, int k, int dtype);
+int htrvt_mixer_reduce_rows(int64_t rows, int D, int dtype);
+int htrvt_mixer_fwd_train(const void* u, const float* w, void* c, float* partial, int B, int N, int D, int k, int dtype,
+                          void* stream);
+int htrvt_mixer_bn_silu(const void* c, const float* scale, const float* shift, void* s, int64_t rows, int D, int dtype,
+                        void* stream);
+int htrvt_mixer_fwd_eval(const void* u, const float* w, const float* scale, const float* shift, void* c, void* s, int B,
+                         int N, int D, int k, int dtype, void* stream);
+int htrvt_mixer_bwd_reduce(const void* ds, const void* c, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, float* partial, int64_t rows, int D, int dtype, void* stream);
+int htrvt_mixer_bwd(const void* u, const void* c, const void* ds, const float* w, const float* scale, const float* shift,
+                    const float* coef, void* du, float* dw_partial, float* db_partial, int B, int N, int D, int k, int dtype,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
