@@ -172,7 +172,10 @@ extern "C" int htrvt_ctc_greedy_decode(const float* logits, int B, int T, int C,
                                        int32_t* out_len, void* stream) {
   HTRVT_REQUIRE(B > 0 && T > 0 && C > 0 && ld >= C && T <= 16384, "htrvt_ctc_greedy_decode: bad shape B=%d T=%d C=%d", B, T, C);
   const int nth = T >= 1024 ? 1024 : ((T + 63) / 64) * 64;
-  hipLaunchKernelGGL(greedy_decode_kernel, dim3(B), dim3(nth), 2 * T * sizeof(int), (hipStream_t)stream, logits, T, C,
+  const size_t smem = 2 * (size_t)T * sizeof(int);   // 128 KB at the limit: more than 64 KB needs the attribute
+  if (smem > 64 * 1024)
+    if (int rc = allow_dynamic_lds<greedy_decode_kernel>(2 * 16384 * (int)sizeof(int), "htrvt_ctc_greedy_decode")) return rc;
+  hipLaunchKernelGGL(greedy_decode_kernel, dim3(B), dim3(nth), smem, (hipStream_t)stream, logits, T, C,
                      (long long)ld, ncharacter, out, out_len);
   return check_launch("ctc_greedy_decode");
 }
