@@ -134,6 +134,13 @@ PROTOTYPES = {
     "htrvt_sgm_query_bwd_workspace_floats": (i64, [i32, i32, i32, i32]),
     "htrvt_sgm_query_bwd": (i32, [vp] * 7 + [i32, i32, i32, i32, i32, i32, vp]),
     "htrvt_sgm_dropout": (i32, [vp, vp, i64, vp, f32, i32, vp]),
+    "htrvt_attn_dropout_supported": (i32, [i32, i32, i32]),
+    "htrvt_attn_dropout_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp, f32, i32, vp]),
+    "htrvt_attn_dropout_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, f32, i32, vp]),
+    "htrvt_attn_relpos_dropout_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, f32, i32, vp]),
+    "htrvt_attn_relpos_dropout_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, f32,
+                                            i32, vp]),
+    "htrvt_residual_dropout": (i32, [vp, vp, vp, i32, i64, i32, vp, f32, f32, i32, vp]),
     "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "htrvt_sgm_xent_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "htrvt_sgm_convert": (i32, [vp, i32, vp, i32, i64, i32, vp]),

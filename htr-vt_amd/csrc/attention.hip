@@ -134,29 +134,34 @@ struct DenseScores : NoExtras {
   }
 };
 
-template <int HD, class Src>
-int launch_fwd(const AttnParams& p, hipStream_t st) {
+template <class Drop>
+using Launched = typename Drop::template Params<AttnParams>;
+
+template <int HD, class Src, class Drop>
+int launch_fwd(const Launched<Drop>& p, hipStream_t st) {
   constexpr int smem = 2 * 2 * KT * HD * 2;
-  if (int rc = allow_dynamic_lds<attn_fwd_kernel<HD, Src>>(smem, "attn_fwd")) return rc;
-  hipLaunchKernelGGL((attn_fwd_kernel<HD, Src>), dim3(p.B * p.h * ((p.N + 127) / 128)), dim3(256), smem, st, p);
+  if (int rc = allow_dynamic_lds<attn_fwd_kernel<HD, Src, Drop>>(smem, "attn_fwd")) return rc;
+  hipLaunchKernelGGL((attn_fwd_kernel<HD, Src, Drop>), dim3(p.B * p.h * ((p.N + 127) / 128)), dim3(256), smem, st, p);
   return check_launch("attn_fwd");
 }
 
-template <int HD, class Src>
-int launch_bwd(const AttnParams& p, float* delta, hipStream_t st) {
+template <int HD, class Src, class Drop>
+int launch_bwd(const Launched<Drop>& p, float* delta, hipStream_t st) {
   constexpr int smem_dq = 2 * 2 * KT * HD * 2, smem_kv = 2 * DkvGeom<HD>::STAGE_B;
-  if (int rc = allow_dynamic_lds<attn_bwd_dq_kernel<HD, Src>>(smem_dq, "attn_bwd_dq")) return rc;
-  if (int rc = allow_dynamic_lds<attn_bwd_dkv_kernel<HD, Src>>(smem_kv, "attn_bwd_dkv")) return rc;
+  if (int rc = allow_dynamic_lds<attn_bwd_dq_kernel<HD, Src, Drop>>(smem_dq, "attn_bwd_dq")) return rc;
+  if (int rc = allow_dynamic_lds<attn_bwd_dkv_kernel<HD, Src, Drop>>(smem_kv, "attn_bwd_dkv")) return rc;
   const dim3 grid(p.B * p.h * ((p.N + 127) / 128));
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, Src>), grid, dim3(256), smem_dq, st, p, delta);
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, Src>), grid, dim3(256), smem_kv, st, p, (const float*)delta);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, Src, Drop>), grid, dim3(256), smem_dq, st, p, delta);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HD, Src, Drop>), grid, dim3(256), smem_kv, st, p, (const float*)delta);
   return check_launch("attn_bwd");
 }
 
-template <class Src>
-int launch(const AttnParams& p, int hd, float* delta, hipStream_t st) {     // delta == NULL: the forward
-  if (delta == nullptr) return hd == 128 ? launch_fwd<128, Src>(p, st) : hd == 64 ? launch_fwd<64, Src>(p, st) : launch_fwd<32, Src>(p, st);
-  return hd == 128 ? launch_bwd<128, Src>(p, delta, st) : hd == 64 ? launch_bwd<64, Src>(p, delta, st) : launch_bwd<32, Src>(p, delta, st);
+template <class Src, class Drop = NoDrop>
+int launch(const Launched<Drop>& p, int hd, float* delta, hipStream_t st) {     // delta == NULL: the forward
+  if (delta == nullptr)
+    return hd == 128 ? launch_fwd<128, Src, Drop>(p, st) : hd == 64 ? launch_fwd<64, Src, Drop>(p, st) : launch_fwd<32, Src, Drop>(p, st);
+  return hd == 128 ? launch_bwd<128, Src, Drop>(p, delta, st) : hd == 64 ? launch_bwd<64, Src, Drop>(p, delta, st)
+                                                                         : launch_bwd<32, Src, Drop>(p, delta, st);
 }
 
 AttnParams make_params(const void* qkv, const float* bias, int B, int N, int heads, float scale) {
@@ -167,6 +172,16 @@ AttnParams make_params(const void* qkv, const float* bias, int B, int N, int hea
   p.scale = scale;
   p.sl2 = scale * LOG2E;
   return p;
+}
+
+DropParams<AttnParams> with_dropout(const AttnParams& a, const int64_t* seed, float p) {
+  DropParams<AttnParams> d{};
+  static_cast<AttnParams&>(d) = a;
+  const DropRate dr = drop_rate(p);
+  d.seed = (const long long*)seed;
+  d.thr = dr.thr;
+  d.keep_scale = dr.scale;
+  return d;
 }
 
 }  // namespace
@@ -208,4 +223,38 @@ extern "C" int htrvt_attn_bwd(const void* qkv, const float* bias, const void* ou
   p.dbias = dbias;
   hipStream_t st = (hipStream_t)stream;
   return bias != nullptr ? launch<DenseScores>(p, hd, delta, st) : launch<PlainScores>(p, hd, delta, st);
+}
+
+// ---- dropout on the probabilities (plain scores): the mask of dropout_common.h regenerated in all three kernels ------------
+extern "C" int htrvt_attn_dropout_supported(int N, int hd, int dtype) { return htrvt_attn_supported(N, hd, dtype); }
+
+extern "C" int htrvt_attn_dropout_fwd(const void* qkv, void* out, float* lse2, int B, int N, int heads, int hd, float scale,
+                                      const int64_t* seed, float p, int dtype, void* stream) {
+  HTRVT_REQUIRE(p >= 0.f && p < 1.f, "htrvt_attn_dropout_fwd: p=%g outside [0, 1)", (double)p);
+  if (p == 0.f) return htrvt_attn_fwd(qkv, nullptr, out, lse2, B, N, heads, hd, scale, dtype, stream);
+  HTRVT_REQUIRE(qkv && out && seed, "htrvt_attn_dropout_fwd: null operand");
+  HTRVT_REQUIRE(B > 0 && heads > 0 && htrvt_attn_dropout_supported(N, hd, dtype),
+                "htrvt_attn_dropout_fwd: unsupported shape/dtype (N=%d >= 32, hd=%d in {32,64,128}, bfloat16)", N, hd);
+  HTRVT_REQUIRE((long long)B * N * 3 * heads * hd < (1ll << 31), "htrvt_attn_dropout_fwd: qkv too large");
+  AttnParams a = make_params(qkv, nullptr, B, N, heads, scale);
+  a.out = (bf16_t*)out;
+  a.lse2 = lse2;
+  return launch<PlainScores, HashDrop>(with_dropout(a, seed, p), hd, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int htrvt_attn_dropout_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, float* delta,
+                                      void* dqkv, int B, int N, int heads, int hd, float scale, const int64_t* seed, float p,
+                                      int dtype, void* stream) {
+  HTRVT_REQUIRE(p >= 0.f && p < 1.f, "htrvt_attn_dropout_bwd: p=%g outside [0, 1)", (double)p);
+  if (p == 0.f) return htrvt_attn_bwd(qkv, nullptr, out, dout, lse2, delta, dqkv, nullptr, B, N, heads, hd, scale, dtype, stream);
+  HTRVT_REQUIRE(qkv && out && dout && lse2 && delta && dqkv && seed, "htrvt_attn_dropout_bwd: null operand");
+  HTRVT_REQUIRE(B > 0 && heads > 0 && htrvt_attn_dropout_supported(N, hd, dtype),
+                "htrvt_attn_dropout_bwd: unsupported shape/dtype (N=%d >= 32, hd=%d in {32,64,128}, bfloat16)", N, hd);
+  HTRVT_REQUIRE((long long)B * N * 3 * heads * hd < (1ll << 31), "htrvt_attn_dropout_bwd: qkv too large");
+  AttnParams a = make_params(qkv, nullptr, B, N, heads, scale);
+  a.out = (bf16_t*)const_cast<void*>(out);
+  a.dout = (const bf16_t*)dout;
+  a.lse2 = const_cast<float*>(lse2);
+  a.dqkv = (bf16_t*)dqkv;
+  return launch<PlainScores, HashDrop>(with_dropout(a, seed, p), hd, delta, (hipStream_t)stream);
 }

@@ -27,9 +27,19 @@
 //   dq_scores, dq_block, dq_end raw S^T, dP^T of a 32-key block -> dS^T in dp (d(score) in st); bias-gradient hooks
 //   dkv_quad, dkv_prob, dkv_dbias  dK/dV launch: what the source keeps per register quad (four queries); P of a pair from its
 //                               raw score; the pair's d(score) for the bias gradient
+//
+// Dropout on the probabilities is a third template parameter, a policy `Drop` (NoDrop by default: every statement it adds
+// sits behind `if constexpr (Drop::ON)`, and the kernel parameter is Src::Params itself).  HashDrop regenerates the mask
+// of dropout_common.h in all three kernels from the pair's logical coordinates,
+//     keep(b, head, q, k) = keep_elem(seed, ((b h + head) N + q) N + k, thr),
+// which is what htrvt_sgm_dropout draws on a dense [B h][N][N] tensor.  Forward: the row sum and lse2 use the undropped
+// P, the P fed to O^T += V^T P^T is keep ? P : 0 and 1 / (1 - p) goes into the final 1 / l.  Backward: dP <- keep ?
+// dP / (1 - p) : 0 in front of the source's d(score) (delta = rowsum(dO * O) already equals sum_k P M / (1 - p) dP), and
+// dV accumulates dO^T (P M / (1 - p)).
 #pragma once
 
 #include "attention_common.h"
+#include "dropout_common.h"
 
 namespace {
 
@@ -69,6 +79,32 @@ __device__ __forceinline__ void place_lane(Where& w) {
   w.r = w.lane & 31, w.hf = w.lane >> 5;
 }
 
+// dropout policies.  Params<P>: the kernel parameter over the source's P
+struct NoDrop {
+  static constexpr bool ON = false;
+  static constexpr bool grouped(int) { return true; }      // dK/dV: may a GROUPED source keep its grouping?
+  template <class P> using Params = P;
+};
+
+template <class P>
+struct DropParams : P {
+  const long long* seed;   // int64 on the device
+  unsigned thr;            // drop_rate(p)
+  float keep_scale;
+};
+
+struct HashDrop {
+  static constexpr bool ON = true;
+  // dK/dV at hd 128 holds 400 registers grouped; with the 64-bit hash state beside the up-front fragments it spilled 63
+  static constexpr bool grouped(int hd) { return hd < 128; }
+  template <class P> using Params = DropParams<P>;
+  // hash input of the pair (row, 0) of head bh; one column further adds DROP_G, one row further DROP_G * N
+  template <class P>
+  static __device__ __forceinline__ unsigned long long row_input(const P& p, int bh, int row) {
+    return hash_input((unsigned long long)p.seed[0], ((unsigned long long)bh * p.N + row) * p.N);
+  }
+};
+
 // plain and dense-bias scores visit every staged tile
 struct AllTiles {
   __device__ __forceinline__ int first_tile(int, int, int) const { return 0; }
@@ -79,8 +115,8 @@ struct AllTiles {
 // -------------------------------------------------------------------------------------------------------------------
 // forward
 // -------------------------------------------------------------------------------------------------------------------
-template <int HD, class Src>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Src::Params p) {
+template <int HD, class Src, class Drop = NoDrop>
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Drop::template Params<typename Src::Params> p) {
   constexpr int NTH = 256, QB = 128;
   constexpr int TILE_B = KT * HD * 2;
   constexpr int NS = HD / 16;       // k-steps of the QK^T product
@@ -123,6 +159,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Src::Pa
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
   float m = -INFINITY, l = 0.f;     // running max (scaled base-2 domain) and this lane half's share of the running sum
+  unsigned long long zrow = 0;      // dropout: hash input of (this lane's query, key 4 hf)
+  if constexpr (Drop::ON) zrow = Drop::row_input(p, w.bh, q0 + r) + DROP_G * (unsigned long long)(4 * hf);
 
   const int nt = (p.N + KT - 1) / KT;
   for (int it = 0; t < nt; ++it) {
@@ -166,6 +204,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Src::Pa
         for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
     }
     l += rs;
+    if constexpr (Drop::ON) {       // behind the row sum: l and lse2 are those of the undropped P
+      const unsigned long long zt = zrow + DROP_G * (unsigned long long)(t * KT);
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (!keep_hashed(zt + DROP_G * (unsigned long long)(32 * c + (i & 3) + 8 * (i >> 2)), p.thr)) st[c][i] = 0.f;
+    }
     // O^T += V^T P^T
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -183,7 +229,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Src::Pa
   }
 
   l += xhalf(l);
-  const float inv = 1.0f / l;
+  float inv = 1.0f / l;
+  if constexpr (Drop::ON) inv *= p.keep_scale;
   if (q0 + r <= last) {
     store_lane_rows<ND>(o, p.out + ((long long)b * p.N + q0 + r) * ((long long)p.h * HD) + hh * HD, hf, inv);
     if (hf == 0 && p.lse2 != nullptr) p.lse2[(long long)w.bh * p.N + q0 + r] = m + log2f(l);
@@ -195,8 +242,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const typename Src::Pa
 // lane owns one query, K / V tiles stream through LDS, P is recomputed from the saved lse2.
 //   S^T = K Q^T ; P^T = exp2(S^T sl2 - lse2[q]) ; dP^T = V dO^T ; dS^T = P^T (dP^T - delta[q]) scale ; dQ^T += K^T dS^T
 // -------------------------------------------------------------------------------------------------------------------
-template <int HD, class Src>
-__global__ __launch_bounds__(256, Src::dq_wgs(HD)) void attn_bwd_dq_kernel(const typename Src::Params p, float* __restrict__ delta) {
+template <int HD, class Src, class Drop = NoDrop>
+__global__ __launch_bounds__(256, Src::dq_wgs(HD)) void attn_bwd_dq_kernel(const typename Drop::template Params<typename Src::Params> p,
+                                                                          float* __restrict__ delta) {
   constexpr int NTH = 256, QB = 128;
   constexpr int TILE_B = KT * HD * 2;
   constexpr int NS = HD / 16, ND = HD / 32;
@@ -252,6 +300,8 @@ __global__ __launch_bounds__(256, Src::dq_wgs(HD)) void attn_bwd_dq_kernel(const
   for (int d = 0; d < ND; ++d)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dq[d][i] = 0.f;
+  unsigned long long zrow = 0;      // dropout: hash input of (this lane's query, key 4 hf)
+  if constexpr (Drop::ON) zrow = Drop::row_input(p, w.bh, q0 + r) + DROP_G * (unsigned long long)(4 * hf);
 
   const int nt = (p.N + KT - 1) / KT;
   for (int it = 0; t < nt; ++it) {
@@ -271,6 +321,12 @@ __global__ __launch_bounds__(256, Src::dq_wgs(HD)) void attn_bwd_dq_kernel(const
       for (int s = 0; s < NS; ++s) {
         st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<HD>(kt, la, 32 * c, s), qf[s], st, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag<HD>(vt, la, 32 * c, s), dof[s], dp, 0, 0, 0);
+      }
+      if constexpr (Drop::ON) {     // dP of the dropped pairs is 0, of the kept ones dP / (1 - p)
+        const unsigned long long zt = zrow + DROP_G * (unsigned long long)(t * KT + 32 * c);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          dp[i] = keep_hashed(zt + DROP_G * (unsigned long long)((i & 3) + 8 * (i >> 2)), p.thr) ? dp[i] * p.keep_scale : 0.f;
       }
       src.dq_scores(st, dp, t, nt, c, lse, dl);
       src.dq_block(st, t, c);
@@ -308,11 +364,13 @@ struct DkvGeom {
   static constexpr int STAGE_B = 2 * TILE_B + 2 * QT * 4 + 16;     // Q tile | dO tile | lse2[QT] | delta[QT] | dump word
 };
 
-template <int HD, class Src>
-__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const typename Src::Params p, const float* __restrict__ delta) {
+template <int HD, class Src, class Drop = NoDrop>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const typename Drop::template Params<typename Src::Params> p,
+                                                              const float* __restrict__ delta) {
   constexpr int NTH = 256, KB = 128, QT = DkvGeom<HD>::QT;
   constexpr int TILE_B = DkvGeom<HD>::TILE_B, STAGE_B = DkvGeom<HD>::STAGE_B;
   constexpr int NS = HD / 16, ND = HD / 32;
+  constexpr bool GROUPED = Src::GROUPED && Drop::grouped(HD);
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][Q | dO | lse2 | delta | dump] | the source's
   Where w;
   place_workgroup(p, w);
@@ -362,6 +420,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const typename Src
   for (int d = 0; d < ND; ++d)
 #pragma unroll
     for (int i = 0; i < 16; ++i) dk[d][i] = dv[d][i] = 0.f;
+  // dropout: hash input of (query 4 hf, this lane's key) and the step of one query (the lanes own keys here)
+  unsigned long long zcol = 0, zstep = 0;
+  if constexpr (Drop::ON) {
+    zstep = DROP_G * (unsigned long long)p.N;
+    zcol = Drop::row_input(p, w.bh, 4 * hf) + DROP_G * (unsigned long long)(k0 + r);
+  }
 
   const int nt = (p.N + QT - 1) / QT;
   for (int it = 0; t < nt; ++it) {
@@ -384,14 +448,14 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const typename Src
       // per-query constants of this 32-query block and the fragments of a whole product are requested first and the MFMAs
       // follow (read -> wait -> MFMA one at a time cost ~150 cycles per MFMA)
       float4 lsq[4], deq[4];
-      if constexpr (Src::GROUPED) {
+      if constexpr (GROUPED) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           lsq[g] = *reinterpret_cast<const float4*>(cst + 32 * c + 8 * g + 4 * hf);
           deq[g] = *reinterpret_cast<const float4*>(cst + QT + 32 * c + 8 * g + 4 * hf);
         }
       }
-      constexpr int NSG = !Src::GROUPED ? 1 : (NS >= 4 ? 4 : NS);      // k-steps whose fragments are requested together
+      constexpr int NSG = !GROUPED ? 1 : (NS >= 4 ? 4 : NS);      // k-steps whose fragments are requested together
 #pragma unroll
       for (int s0 = 0; s0 < NS; s0 += NSG) {
         bf16x8_t fq[NSG], fd[NSG];
@@ -409,23 +473,29 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(const typename Src
       // accumulator register i is query 32 c + (i & 3) + 8 (i >> 2) + 4 hf of the tile
       static_for<0, 4>([&](auto G) {
         constexpr int g = decltype(G)::value;
-        const float4 ls = Src::GROUPED ? lsq[g] : *reinterpret_cast<const float4*>(cst + 32 * c + 8 * g + 4 * hf);
-        const float4 de = Src::GROUPED ? deq[g] : *reinterpret_cast<const float4*>(cst + QT + 32 * c + 8 * g + 4 * hf);
+        const float4 ls = GROUPED ? lsq[g] : *reinterpret_cast<const float4*>(cst + 32 * c + 8 * g + 4 * hf);
+        const float4 de = GROUPED ? deq[g] : *reinterpret_cast<const float4*>(cst + QT + 32 * c + 8 * g + 4 * hf);
         const float lsv[4] = {ls.x, ls.y, ls.z, ls.w}, dev[4] = {de.x, de.y, de.z, de.w};
         const auto quad = src.dkv_quad(t * QT, 32 * c + 8 * g);      // queries (tile's first) + (offset) + 4 hf + 0 .. 3
         static_for<0, 4>([&](auto J) {
           constexpr int j = decltype(J)::value, i = 4 * g + j;
           const float pr = src.dkv_prob(quad, j, st[i], lsv[j]);            // (a padding query carries lse2 = +inf: pr = 0)
-          const float dsu = pr * (dp[i] - dev[j]);                          // d(score): gradient of the bias entry too
+          float pv = pr, dpi = dp[i];
+          if constexpr (Drop::ON) {
+            const bool keep = keep_hashed(zcol + zstep * (unsigned long long)(t * QT + 32 * c + 8 * g + j), p.thr);
+            pv = keep ? pr * p.keep_scale : 0.f;
+            dpi = keep ? dpi * p.keep_scale : 0.f;
+          }
+          const float dsu = pr * (dpi - dev[j]);                            // d(score): gradient of the bias entry too
           src.dkv_dbias(quad, j, dsu);
-          st[i] = pr;                                                       // P
+          st[i] = pv;                                                       // P (dropout: P M / (1 - p), what multiplied V)
           dp[i] = dsu * p.scale;                                            // dS
         });
       });
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const bf16x8_t pb = acc_frag(st, s), dsb = acc_frag(dp, s);
-        if constexpr (Src::GROUPED) {       // the transposed fragments of a k-step are read before its MFMAs
+        if constexpr (GROUPED) {       // the transposed fragments of a k-step are read before its MFMAs
           bf16x8_t tv[ND], tk[ND];
 #pragma unroll
           for (int d = 0; d < ND; ++d) {

@@ -282,24 +282,37 @@ RelParams make_params(const void* qkv, const float* table, int B, int N, int hea
   return p;
 }
 
+DropParams<RelParams> with_dropout(const RelParams& r, const int64_t* seed, float p) {
+  DropParams<RelParams> d{};
+  static_cast<RelParams&>(d) = r;
+  const DropRate dr = drop_rate(p);
+  d.seed = (const long long*)seed;
+  d.thr = dr.thr;
+  d.keep_scale = dr.scale;
+  return d;
+}
+
 int fwd_lds(int hd, const RelParams& p) { return 2 * 2 * KT * hd * 2 + 4 * p.ncode + 4 * tab_floats(p.P); }
 int dq_lds(int hd, const RelParams& p) { return fwd_lds(hd, p) + 4 * 4 * (ceil_div(p.N, KT) * KT + 32) + 4 * 4 * 32 * 33; }
 int dkv_lds(int hd, const RelParams& p) {
   return 2 * (hd == 128 ? DkvGeom<128>::STAGE_B : DkvGeom<64>::STAGE_B) + 4 * p.ncode + 4 * tab_floats(p.P);
 }
 
-template <int HD>
-int launch_fwd(const RelParams& p, hipStream_t st) {
-  constexpr auto kern = attn_fwd_kernel<HD, TableScores>;
+template <class Drop>
+using Launched = typename Drop::template Params<RelParams>;
+
+template <int HD, class Drop>
+int launch_fwd(const Launched<Drop>& p, hipStream_t st) {
+  constexpr auto kern = attn_fwd_kernel<HD, TableScores, Drop>;
   if (int rc = allow_dynamic_lds<kern>(LDS_MAX, "attn_relpos_fwd")) return rc;
   hipLaunchKernelGGL(kern, dim3(p.B * p.h * ceil_div(p.N, 128)), dim3(256), fwd_lds(HD, p), st, p);
   return check_launch("attn_relpos_fwd");
 }
 
-template <int HD>
-int launch_bwd(const RelParams& p, float* delta, float* dtable, hipStream_t st) {
-  constexpr auto kq = attn_bwd_dq_kernel<HD, TableScores>;
-  constexpr auto kkv = attn_bwd_dkv_kernel<HD, TableScores>;
+template <int HD, class Drop>
+int launch_bwd(const Launched<Drop>& p, float* delta, float* dtable, hipStream_t st) {
+  constexpr auto kq = attn_bwd_dq_kernel<HD, TableScores, Drop>;
+  constexpr auto kkv = attn_bwd_dkv_kernel<HD, TableScores, Drop>;
   if (int rc = allow_dynamic_lds<kq>(LDS_MAX, "attn_relpos_bwd_dq")) return rc;
   if (int rc = allow_dynamic_lds<kkv>(LDS_MAX, "attn_relpos_bwd_dkv")) return rc;
   const int nqb = ceil_div(p.N, 128);
@@ -312,6 +325,19 @@ int launch_bwd(const RelParams& p, float* delta, float* dtable, hipStream_t st) 
                        p.B * nqb, ne, p.h);
   }
   return check_launch("attn_relpos_bwd");
+}
+
+// p == 0: the instantiations without dropout (seed is not read)
+template <int HD>
+int launch_fwd_p(const RelParams& r, const int64_t* seed, float p, hipStream_t st) {
+  if (p == 0.f) return launch_fwd<HD, NoDrop>(r, st);
+  return launch_fwd<HD, HashDrop>(with_dropout(r, seed, p), st);
+}
+
+template <int HD>
+int launch_bwd_p(const RelParams& r, const int64_t* seed, float p, float* delta, float* dtable, hipStream_t st) {
+  if (p == 0.f) return launch_bwd<HD, NoDrop>(r, delta, dtable, st);
+  return launch_bwd<HD, HashDrop>(with_dropout(r, seed, p), delta, dtable, st);
 }
 
 }  // namespace
@@ -328,7 +354,16 @@ extern "C" int64_t htrvt_attn_relpos_bwd_workspace_floats(int B, int N, int head
 
 extern "C" int htrvt_attn_relpos_fwd(const void* qkv, const float* table, void* out, float* lse2, int B, int N, int heads,
                                      int hd, float scale, int num_patches, int window, int shift, int dtype, void* stream) {
-  HTRVT_REQUIRE(qkv && table && out, "htrvt_attn_relpos_fwd: null operand");
+  return htrvt_attn_relpos_dropout_fwd(qkv, table, out, lse2, B, N, heads, hd, scale, num_patches, window, shift, nullptr, 0.f,
+                                       dtype, stream);
+}
+
+// dropout on the probabilities: p == 0 is the entry point above, seed (an int64 on the device) may then be NULL
+extern "C" int htrvt_attn_relpos_dropout_fwd(const void* qkv, const float* table, void* out, float* lse2, int B, int N,
+                                             int heads, int hd, float scale, int num_patches, int window, int shift,
+                                             const int64_t* seed, float pdrop, int dtype, void* stream) {
+  HTRVT_REQUIRE(pdrop >= 0.f && pdrop < 1.f, "htrvt_attn_relpos_fwd: dropout p=%g outside [0, 1)", (double)pdrop);
+  HTRVT_REQUIRE(qkv && table && out && (seed || pdrop == 0.f), "htrvt_attn_relpos_fwd: null operand");
   if (int rc = check_geometry(N, hd, dtype, num_patches, window, shift, "htrvt_attn_relpos_fwd")) return rc;
   HTRVT_REQUIRE(B > 0 && heads > 0, "htrvt_attn_relpos_fwd: B=%d heads=%d", B, heads);
   HTRVT_REQUIRE((long long)B * N * 3 * heads * hd < (1ll << 31), "htrvt_attn_relpos_fwd: qkv too large");
@@ -337,13 +372,22 @@ extern "C" int htrvt_attn_relpos_fwd(const void* qkv, const float* table, void* 
   p.lse2 = lse2;
   HTRVT_REQUIRE(fwd_lds(hd, p) <= LDS_MAX, "htrvt_attn_relpos_fwd: %d B of LDS", fwd_lds(hd, p));
   hipStream_t st = (hipStream_t)stream;
-  return hd == 128 ? launch_fwd<128>(p, st) : launch_fwd<64>(p, st);
+  return hd == 128 ? launch_fwd_p<128>(p, seed, pdrop, st) : launch_fwd_p<64>(p, seed, pdrop, st);
 }
 
 extern "C" int htrvt_attn_relpos_bwd(const void* qkv, const float* table, const void* out, const void* dout, const float* lse2,
                                      float* delta, void* dqkv, float* dtable, float* workspace, int B, int N, int heads, int hd,
                                      float scale, int num_patches, int window, int shift, int dtype, void* stream) {
-  HTRVT_REQUIRE(qkv && table && out && dout && lse2 && delta && dqkv, "htrvt_attn_relpos_bwd: null operand");
+  return htrvt_attn_relpos_dropout_bwd(qkv, table, out, dout, lse2, delta, dqkv, dtable, workspace, B, N, heads, hd, scale,
+                                       num_patches, window, shift, nullptr, 0.f, dtype, stream);
+}
+
+extern "C" int htrvt_attn_relpos_dropout_bwd(const void* qkv, const float* table, const void* out, const void* dout,
+                                             const float* lse2, float* delta, void* dqkv, float* dtable, float* workspace, int B,
+                                             int N, int heads, int hd, float scale, int num_patches, int window, int shift,
+                                             const int64_t* seed, float pdrop, int dtype, void* stream) {
+  HTRVT_REQUIRE(pdrop >= 0.f && pdrop < 1.f, "htrvt_attn_relpos_bwd: dropout p=%g outside [0, 1)", (double)pdrop);
+  HTRVT_REQUIRE(qkv && table && out && dout && lse2 && delta && dqkv && (seed || pdrop == 0.f), "htrvt_attn_relpos_bwd: null operand");
   HTRVT_REQUIRE(dtable == nullptr || workspace != nullptr, "htrvt_attn_relpos_bwd: dtable needs the workspace");
   if (int rc = check_geometry(N, hd, dtype, num_patches, window, shift, "htrvt_attn_relpos_bwd")) return rc;
   HTRVT_REQUIRE(B > 0 && heads > 0, "htrvt_attn_relpos_bwd: B=%d heads=%d", B, heads);
@@ -357,5 +401,5 @@ extern "C" int htrvt_attn_relpos_bwd(const void* qkv, const float* table, const 
   HTRVT_REQUIRE(dq_lds(hd, p) <= LDS_MAX && dkv_lds(hd, p) <= LDS_MAX, "htrvt_attn_relpos_bwd: %d / %d B of LDS",
                 dq_lds(hd, p), dkv_lds(hd, p));
   hipStream_t st = (hipStream_t)stream;
-  return hd == 128 ? launch_bwd<128>(p, delta, dtable, st) : launch_bwd<64>(p, delta, dtable, st);
+  return hd == 128 ? launch_bwd_p<128>(p, seed, pdrop, delta, dtable, st) : launch_bwd_p<64>(p, seed, pdrop, delta, dtable, st);
 }

@@ -11,6 +11,7 @@
 //                          an ordered fixed-shape reduction to the scalar loss, and d logits
 //   htrvt_sgm_convert      dst (+)= src between float32 / bfloat16 buffers (the model's feature tap and its gradient)
 #include "common.h"
+#include "dropout_common.h"
 
 using namespace htrvt;
 
@@ -128,16 +129,7 @@ __global__ __launch_bounds__(NT) void sgm_query_bwd_final_kernel(const float* __
 }
 
 // ------------------------------------------------------------------ dropout
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ bool keep_elem(unsigned long long seed, long long i, unsigned thr) {
-  const unsigned long long h = mix64(seed + 0x9e3779b97f4a7c15ull * (unsigned long long)(i + 1));
-  return (unsigned)(h >> 40) >= thr;   // 24 uniform bits: P(keep) = 1 - thr / 2^24
-}
-
+// (the mask: dropout_common.h)
 template <typename T>
 __global__ __launch_bounds__(NT) void sgm_dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long long nvec,
                                                          const long long* __restrict__ seed_dev, unsigned thr, float scale) {
@@ -305,8 +297,7 @@ extern "C" int htrvt_sgm_dropout(const void* x, void* y, int64_t n, const int64_
   HTRVT_REQUIRE(n % ch == 0, "htrvt_sgm_dropout: n=%lld not a multiple of %d", (long long)n, ch);
   if (n == 0) return 0;
   HTRVT_REQUIRE(x && y && seed, "htrvt_sgm_dropout: null buffer");
-  const unsigned thr = (unsigned)((double)p * 16777216.0 + 0.5);
-  const float scale = (float)(1.0 / (1.0 - (double)p));
+  const auto [thr, scale] = drop_rate(p);
   const long long nvec = n / ch;
   if (dtype == HTRVT_BF16)
     hipLaunchKernelGGL(sgm_dropout_kernel<bf16_t>, dim3(blocks_for(nvec)), dim3(NT), 0, (hipStream_t)stream,

@@ -5,7 +5,12 @@ torch.empty on their input's device, and a forward returns what its backward tak
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
 here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, and the autograd wrappers of variants.py.
 
-Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5."""
+Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5.
+
+Dropout on the attention probabilities is the keyword `drop=(seed, p)` of the self-attention functions: seed an int64
+device tensor of one element, p in (0, 1).  The mask is keep_elem(seed, ((b h + head) N + q) N + k) (csrc/dropout_common.h)
+on every route -- regenerated inside the fused kernels, drawn by htrvt_sgm_dropout on P and dP in the unfused one -- and a
+backward takes the forward's `drop`.  drop=None is the call without dropout, untouched."""
 import torch
 
 from ._lib import check, lib
@@ -36,6 +41,23 @@ def linear_wgrad(dy, x, rows):
     db = torch.zeros(N, dtype=torch.float32, device=dy.device)
     colsum(dy, rows, N, N, db, dti=dt(dy.dtype))
     return dw, db
+
+
+def dropout(x, seed, p):
+    """x * keep / (1 - p) with the counter-based mask of (seed, element index); its backward is the same call on dy"""
+    y = torch.empty_like(x)
+    check(lib.htrvt_sgm_dropout(ptr(x), ptr(y), x.numel(), ptr(seed), p, dt(x.dtype), stream()), "sgm_dropout")
+    return y
+
+
+def residual_dropout(x, res, rows_per_sample, seeds, p, p_path):
+    """res + drop_path(dropout(x)) in one pass over x [rows, D]: element-wise dropout p keyed by (seeds[0], element), the
+    whole branch of sample row // rows_per_sample dropped with p_path keyed by (seeds[1], sample).  res=None: without
+    the add, which is the backward (dx from dy).  seeds: int64 device tensor of two elements, None when both p are 0."""
+    y = torch.empty_like(x)
+    check(lib.htrvt_residual_dropout(ptr(x), ptr(res), ptr(y), rows_per_sample, x.numel(), x.shape[-1], ptr(seeds), p, p_path,
+                                     dt(x.dtype), stream()), "residual_dropout")
+    return y
 
 
 def _heads(qkv, h):
@@ -74,21 +96,36 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None):
 
 # ---- self-attention, fused (csrc/attention.hip): scores / probabilities stay on chip -----------------------------------
 
-def attention_fwd(qkv, B, N, h, bias=None, save=True):
-    """(out [B*N, D], lse [B*h, N] or None); bias: None or dense float32 [h, N, N]"""
+def _plain_only(bias, drop):
+    if drop is not None and bias is not None:
+        raise ValueError("fused attention: dropout with a dense score bias is not served (the table kernels or the unfused route)")
+
+
+def attention_fwd(qkv, B, N, h, bias=None, save=True, drop=None):
+    """(out [B*N, D], lse [B*h, N] or None); bias: None or dense float32 [h, N, N]; drop: (seed, p), plain scores only"""
     D, hd = _heads(qkv, h)
     out = _like(qkv, B * N, D)
     lse = _f32(qkv, B * h, N) if save else None
+    _plain_only(bias, drop)
+    if drop is not None:
+        check(lib.htrvt_attn_dropout_fwd(ptr(qkv), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, ptr(drop[0]), drop[1],
+                                         dt(qkv.dtype), stream()), "attn_dropout_fwd")
+        return out, lse
     check(lib.htrvt_attn_fwd(ptr(qkv), ptr(bias), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, dt(qkv.dtype), stream()),
           "attn_fwd")
     return out, lse
 
 
-def attention_bwd(qkv, out, dout, lse, B, N, h, bias=None, dbias=None):
+def attention_bwd(qkv, out, dout, lse, B, N, h, bias=None, dbias=None, drop=None):
     """dqkv by the recomputing backward; dbias (float32 [h, N, N]) += d(score) summed over the batch"""
     hd = _heads(qkv, h)[1]
     dqkv = torch.empty_like(qkv)
     delta = _f32(qkv, B * h, N)
+    _plain_only(bias, drop)
+    if drop is not None:
+        check(lib.htrvt_attn_dropout_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), B, N, h, hd,
+                                         hd ** -0.5, ptr(drop[0]), drop[1], dt(qkv.dtype), stream()), "attn_dropout_bwd")
+        return dqkv
     check(lib.htrvt_attn_bwd(ptr(qkv), ptr(bias), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dbias), B, N, h,
                              hd, hd ** -0.5, dt(qkv.dtype), stream()), "attn_bwd")
     return dqkv
@@ -96,8 +133,9 @@ def attention_bwd(qkv, out, dout, lse, B, N, h, bias=None, dbias=None):
 
 # ---- self-attention as batched GEMMs + row softmax: float32, and shapes the fused kernels do not serve -----------------
 
-def attention_unfused_fwd(qkv, B, N, h, bias=None):
-    """S = scale q k^T, P = softmax(S + bias), out = P v -> (out, P [B*h, N, N], kept for the backward)"""
+def attention_unfused_fwd(qkv, B, N, h, bias=None, drop=None):
+    """S = scale q k^T, P = softmax(S + bias), out = P v -> (out, P [B*h, N, N], kept for the backward).  drop: out =
+    dropout(P) v; the P returned is the undropped one (the backward redraws the mask)"""
     D, hd = _heads(qkv, h)
     out = _like(qkv, B * N, D)
     S = _f32(qkv, B * h, N, N)
@@ -107,25 +145,28 @@ def attention_unfused_fwd(qkv, B, N, h, bias=None):
     check(lib.htrvt_softmax_rows(ptr(S), ptr(P), B * h * N, N, dt(qkv.dtype), ptr(bias), h * N if bias is not None else 0,
                                  stream()), "softmax_rows")
     del S
-    gemm(P, qkv, out, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * h,
+    Pv = P if drop is None else dropout(P, *drop)
+    gemm(Pv, qkv, out, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=3 * D, ldc=D, b_layout=MNMAJOR, batch=B * h,
          batch_inner=h, sA=(h * N * N, N * N), sB=(N * 3 * D, hd), sC=(N * D, hd), b_off=2 * D)
     return out, P
 
 
-def attention_unfused_bwd(qkv, P, dout, B, N, h, dbias=None):
+def attention_unfused_bwd(qkv, P, dout, B, N, h, dbias=None, drop=None):
     """dqkv over the saved P.  Without dbias the score scale goes into the softmax backward; with dbias (float32
     [h, N, N], += d(score) summed over the batch) dS stays unscaled and the dQ / dK GEMMs carry the scale."""
     D, hd = _heads(qkv, h)
     scale = hd ** -0.5
     dqkv = torch.empty_like(qkv)
     bstr = dict(batch=B * h, batch_inner=h)
-    # dV = P^T dO
-    gemm(P, dout, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
+    # dV = P^T dO (dropout: the P that multiplied V)
+    gemm(P if drop is None else dropout(P, *drop), dout, dqkv, dtype=qkv.dtype, M=N, N=hd, K=N, lda=N, ldb=D, ldc=3 * D, a_layout=MNMAJOR, b_layout=MNMAJOR,
          sA=(h * N * N, N * N), sB=(N * D, hd), sC=(N * 3 * D, hd), c_off=2 * D, **bstr)
     # dP = dO V^T
     dP = _f32(qkv, B * h, N, N)
     gemm(dout, qkv, dP, dtype=qkv.dtype, M=N, N=N, K=hd, lda=D, ldb=3 * D, ldc=N, sA=(N * D, hd), sB=(N * 3 * D, hd),
          sC=(h * N * N, N * N), b_off=2 * D, c_f32=True, **bstr)
+    if drop is not None:
+        dP = dropout(dP, *drop)
     dS = _like(qkv, B * h, N, N)
     s_in, s_out = (scale, 1.0) if dbias is None else (1.0, scale)
     check(lib.htrvt_softmax_bwd_rows(ptr(P), ptr(dP), ptr(dS), B * h * N, N, s_in, dt(qkv.dtype), stream()),
@@ -150,22 +191,32 @@ def relpos_workspace_floats(B, N, h, num_patches, window=0, shift=0):
     return n
 
 
-def relpos_attention_fwd(qkv, table, B, N, h, num_patches, window, shift, save=True):
+def relpos_attention_fwd(qkv, table, B, N, h, num_patches, window, shift, save=True, drop=None):
     """table-driven fused kernels (csrc/attn_relpos.hip, bfloat16): (out, lse or None)"""
     D, hd = _heads(qkv, h)
     out = _like(qkv, B * N, D)
     lse = _f32(qkv, B * h, N) if save else None
+    if drop is not None:
+        check(lib.htrvt_attn_relpos_dropout_fwd(ptr(qkv), ptr(table), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, num_patches,
+                                                window, shift, ptr(drop[0]), drop[1], dt(qkv.dtype), stream()),
+              "attn_relpos_dropout_fwd")
+        return out, lse
     check(lib.htrvt_attn_relpos_fwd(ptr(qkv), ptr(table), ptr(out), ptr(lse), B, N, h, hd, hd ** -0.5, num_patches, window,
                                     shift, dt(qkv.dtype), stream()), "attn_relpos_fwd")
     return out, lse
 
 
-def relpos_attention_bwd(qkv, table, out, dout, lse, B, N, h, num_patches, window, shift, dtable=None):
+def relpos_attention_bwd(qkv, table, out, dout, lse, B, N, h, num_patches, window, shift, dtable=None, drop=None):
     """dqkv; dtable (float32, the table's shape) += the table gradient, None: no table gradient and no workspace"""
     hd = _heads(qkv, h)[1]
     dqkv = torch.empty_like(qkv)
     delta = _f32(qkv, B * h, N)
     work = None if dtable is None else _f32(qkv, relpos_workspace_floats(B, N, h, num_patches, window, shift))
+    if drop is not None:
+        check(lib.htrvt_attn_relpos_dropout_bwd(ptr(qkv), ptr(table), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv),
+                                                ptr(dtable), ptr(work), B, N, h, hd, hd ** -0.5, num_patches, window, shift,
+                                                ptr(drop[0]), drop[1], dt(qkv.dtype), stream()), "attn_relpos_dropout_bwd")
+        return dqkv
     check(lib.htrvt_attn_relpos_bwd(ptr(qkv), ptr(table), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dqkv), ptr(dtable),
                                     ptr(work), B, N, h, hd, hd ** -0.5, num_patches, window, shift, dt(qkv.dtype), stream()),
           "attn_relpos_bwd")

@@ -5,7 +5,9 @@ and SGM head (sgm/model/sgm_head.py) call the same seq_ops functions directly, s
 below exercises the launch sequence the models run.  Wrapped: the window fork's relative-position attention (table
 -driven in bfloat16; in float32 ONE dense bias [heads, N, N], table entries inside a window and MASKED outside, into the
 batched-GEMM route), the SGM head's single-head cross-attention, the LGP block's window-12 attention, pool + norm
-and scaled up-sampling, and the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
+and scaled up-sampling, the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU, and the forks' regularisers
+as operators: dropout on the attention probabilities (self_attention, relpos_self_attention(dropout_p=...)) and
+residual + drop_path(dropout(x)) (residual_dropout); wiring those into the models is not done here.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
 run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
 import torch
 
@@ -21,6 +23,21 @@ def _need_device(*tensors):
     if not all(t.is_cuda for t in tensors):
         raise RuntimeError("htrvt_amd.variants needs device tensors on an MI355X (no CPU fallback); the index bookkeeping "
                            "alone is relative_position_index()")
+
+
+def _drop(dropout_p, seed, device, n=1):
+    """(seed, p) for seq_ops, None for p = 0.  seed=None draws the int64 seed(s) on the device from the CUDA default
+    generator (no host sync), as the mixer and the SGM head do."""
+    p = float(dropout_p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability {p} outside [0, 1)")
+    if p == 0.0:
+        return None
+    if seed is None:
+        seed = torch.randint(0, 2 ** 62, (n,), dtype=torch.int64, device=device)
+    if seed.dtype != torch.int64 or seed.numel() != n or not seed.is_cuda:
+        raise TypeError(f"seed: an int64 device tensor of {n} element(s) expected")
+    return seed.contiguous(), p
 
 
 def relative_position_index(N, num_patches, window_size=0, shift_size=0):
@@ -74,13 +91,17 @@ class _BiasedSelfAttention(torch.autograd.Function):
     """qkv [B*N, 3*heads*hd] (the qkv Linear's output) + dense bias [heads, N, N] -> out [B*N, heads*hd]"""
 
     @staticmethod
-    def forward(ctx, qkv, bias, B, N, heads):
+    def forward(ctx, qkv, bias, B, N, heads, drop=None):
         qkv, bias = qkv.contiguous(), bias.contiguous().float()
-        ctx.fused = bool(lib.htrvt_attn_supported(N, qkv.shape[1] // 3 // heads, dt(qkv.dtype)))
+        # the fused dense-bias kernels have no dropout: with it, the unfused route
+        ctx.fused = drop is None and bool(lib.htrvt_attn_supported(N, qkv.shape[1] // 3 // heads, dt(qkv.dtype)))
+        ctx.drop = drop
         if ctx.fused:
             out, aux = seq_ops.attention_fwd(qkv, B, N, heads, bias=bias)             # aux = lse
-        else:
+        elif drop is None:
             out, aux = seq_ops.attention_unfused_fwd(qkv, B, N, heads, bias=bias)     # aux = P
+        else:
+            out, aux = seq_ops.attention_unfused_fwd(qkv, B, N, heads, bias=bias, drop=drop)
         ctx.save_for_backward(qkv, bias, out, aux)
         ctx.dims = (B, N, heads)
         return out
@@ -92,16 +113,20 @@ class _BiasedSelfAttention(torch.autograd.Function):
         dbias = torch.zeros_like(bias)
         if ctx.fused:
             dqkv = seq_ops.attention_bwd(qkv, out, dout, aux, *ctx.dims, bias=bias, dbias=dbias)
-        else:
+        elif ctx.drop is None:
             dqkv = seq_ops.attention_unfused_bwd(qkv, aux, dout, *ctx.dims, dbias=dbias)
-        return dqkv, dbias, None, None, None
+        else:
+            dqkv = seq_ops.attention_unfused_bwd(qkv, aux, dout, *ctx.dims, dbias=dbias, drop=ctx.drop)
+        return dqkv, dbias, None, None, None, None
 
 
-def biased_self_attention(qkv, bias, B, N, heads):
+def biased_self_attention(qkv, bias, B, N, heads, drop=None):
     """softmax(q k^T * hd^-0.5 + bias) v over qkv [B*N, 3*heads*hd] (layout [B,N,3,heads,hd]); bias [heads, ld, ld] float32
     with ld >= N (see relative_position_bias; columns >= N must hold -1e30).  bfloat16 with hd in {32, 64, 128}: the fused
     kernels, the sequence zero-padded to a multiple of 128 if it is not one (masked keys, dropped queries); otherwise
-    (float32 parity path) batched GEMMs + row softmax at a multiple of 8.  Differentiable in qkv and bias."""
+    (float32 parity path) batched GEMMs + row softmax at a multiple of 8.  Differentiable in qkv and bias.
+    drop = (seed, p): dropout on the probabilities, always on the batched-GEMM route; the mask index ((b heads + head) Np +
+    q) Np + k is formed at the padded length Np the route runs at."""
     _need_device(qkv)
     D3 = qkv.shape[1]
     hd = D3 // 3 // heads
@@ -114,11 +139,12 @@ def biased_self_attention(qkv, bias, B, N, heads):
         padded[:, :N, :N] = bias            # (glue: a strided copy; use relative_position_bias(..., ld=padded_len) to avoid it)
         padded[:, N:, 0] = 0.0
         bias = padded
+    extra = () if drop is None else (drop,)
     if Np == N:
-        return _BiasedSelfAttention.apply(qkv, bias, B, N, heads)
+        return _BiasedSelfAttention.apply(qkv, bias, B, N, heads, *extra)
     qp = torch.zeros(B, Np, D3, dtype=qkv.dtype, device=qkv.device)
     qp[:, :N] = qkv.view(B, N, D3)
-    out = _BiasedSelfAttention.apply(qp.view(B * Np, D3), bias, B, Np, heads)
+    out = _BiasedSelfAttention.apply(qp.view(B * Np, D3), bias, B, Np, heads, *extra)
     return out.view(B, Np, -1)[:, :N].reshape(B * N, -1)
 
 
@@ -127,12 +153,13 @@ class _RelPosSelfAttention(torch.autograd.Function):
     (csrc/attn_relpos.hip), any N >= 32 with no padded copy; the table gradient is reduced without atomics"""
 
     @staticmethod
-    def forward(ctx, qkv, table, B, N, heads, num_patches, window, shift):
+    def forward(ctx, qkv, table, B, N, heads, num_patches, window, shift, drop=None):
         if table.dtype != torch.float32:
             raise TypeError(f"relative-position table: float32 expected (the parameter as stored), got {table.dtype}")
         qkv, table = qkv.contiguous(), table.contiguous()
         ctx.dims = (B, N, heads, num_patches, window, shift)
-        out, lse = seq_ops.relpos_attention_fwd(qkv, table, *ctx.dims)
+        ctx.drop = {} if drop is None else {"drop": drop}
+        out, lse = seq_ops.relpos_attention_fwd(qkv, table, *ctx.dims, **ctx.drop)
         ctx.save_for_backward(qkv, table, out, lse)
         return out
 
@@ -140,8 +167,9 @@ class _RelPosSelfAttention(torch.autograd.Function):
     def backward(ctx, dout):
         qkv, table, out, lse = ctx.saved_tensors
         dtable = torch.zeros_like(table) if ctx.needs_input_grad[1] else None
-        dqkv = seq_ops.relpos_attention_bwd(qkv, table, out, dout.contiguous().to(qkv.dtype), lse, *ctx.dims, dtable=dtable)
-        return dqkv, dtable, None, None, None, None, None, None
+        dqkv = seq_ops.relpos_attention_bwd(qkv, table, out, dout.contiguous().to(qkv.dtype), lse, *ctx.dims, dtable=dtable,
+                                            **ctx.drop)
+        return dqkv, dtable, None, None, None, None, None, None, None
 
 
 def relpos_supported(N, head_dim, dtype, num_patches, window_size=0, shift_size=0):
@@ -149,19 +177,94 @@ def relpos_supported(N, head_dim, dtype, num_patches, window_size=0, shift_size=
     return bool(lib.htrvt_attn_relpos_supported(N, head_dim, dt(dtype), num_patches, window_size, shift_size))
 
 
-def relpos_self_attention(qkv, table, B, N, heads, num_patches, window_size=0, shift_size=0):
+def relpos_self_attention(qkv, table, B, N, heads, num_patches, window_size=0, shift_size=0, dropout_p=0.0, seed=None):
     """Attention.forward + Block._attend of the window fork on the qkv Linear's output: softmax(q k^T hd^-0.5 + table
     bias) v with 1-D (shifted) windows, qkv [B*N, 3*heads*hd] (layout [B,N,3,heads,hd]), table [(2P-1), heads] float32.
     bfloat16: the table-driven fused kernels (no dense bias, no padding); float32 (parity path): the dense bias of
-    relative_position_bias + batched GEMMs and row softmax (biased_self_attention).  Differentiable in qkv and table."""
+    relative_position_bias + batched GEMMs and row softmax (biased_self_attention).  Differentiable in qkv and table.
+    dropout_p > 0: attn_drop of the fork, out = (softmax(.) * keep / (1 - p)) v with keep(b, head, q, k) = keep_elem(seed,
+    ((b heads + head) L + q) L + k); seed: an int64 device tensor of one element, None: drawn on the device.  The fused
+    kernels form the index at L = N; the float32 route runs (and indexes the mask) at L = N rounded up to a multiple of 8,
+    so the two routes share a mask for one seed exactly when N is a multiple of 8."""
     _need_device(qkv, table)
     hd = qkv.shape[1] // 3 // heads
+    drop = _drop(dropout_p, seed, qkv.device)
+    extra = () if drop is None else (drop,)
     if qkv.dtype == torch.bfloat16:
         if not relpos_supported(N, hd, qkv.dtype, num_patches, window_size, shift_size):
             raise ValueError(f"relative-position attention: {lib.htrvt_last_error().decode()}")
-        return _RelPosSelfAttention.apply(qkv, table, B, N, heads, num_patches, window_size, shift_size)
+        return _RelPosSelfAttention.apply(qkv, table, B, N, heads, num_patches, window_size, shift_size, *extra)
     bias = relative_position_bias(table, N, num_patches, window_size, shift_size, ld=padded_len(N, qkv.dtype, hd))
-    return biased_self_attention(qkv, bias, B, N, heads)
+    return biased_self_attention(qkv, bias, B, N, heads, *extra)
+
+
+class _SelfAttention(torch.autograd.Function):
+    """qkv [B*N, 3*heads*hd] -> out [B*N, heads*hd], plain scores; drop = (seed, p) or None"""
+
+    @staticmethod
+    def forward(ctx, qkv, B, N, heads, drop):
+        qkv = qkv.contiguous()
+        ctx.fused = bool(lib.htrvt_attn_dropout_supported(N, qkv.shape[1] // 3 // heads, dt(qkv.dtype)))
+        ctx.dims, ctx.drop = (B, N, heads), drop
+        if ctx.fused:
+            out, aux = seq_ops.attention_fwd(qkv, B, N, heads, drop=drop)             # aux = lse
+        else:
+            out, aux = seq_ops.attention_unfused_fwd(qkv, B, N, heads, drop=drop)     # aux = P
+        ctx.save_for_backward(qkv, out, aux)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, aux = ctx.saved_tensors
+        dout = dout.contiguous().to(qkv.dtype)
+        if ctx.fused:
+            dqkv = seq_ops.attention_bwd(qkv, out, dout, aux, *ctx.dims, drop=ctx.drop)
+        else:
+            dqkv = seq_ops.attention_unfused_bwd(qkv, aux, dout, *ctx.dims, drop=ctx.drop)
+        return dqkv, None, None, None, None
+
+
+def self_attention(qkv, B, N, heads, dropout_p=0.0, seed=None):
+    """softmax(q k^T * hd^-0.5) v of model_v1's Attention on the qkv Linear's output, with the forks' attn_drop: out =
+    (softmax(.) * keep / (1 - p)) v, keep(b, head, q, k) = keep_elem(seed, ((b heads + head) N + q) N + k).  The fused
+    kernels where htrvt_attn_dropout_supported says so (bfloat16, hd in {32, 64, 128}, N >= 32), else batched GEMMs + row
+    softmax with the same mask (float32; N a multiple of 8 there).  seed: int64 device tensor of one element, None: drawn
+    on the device from the CUDA default generator.  The backward regenerates the mask from the seed."""
+    _need_device(qkv)
+    hd = qkv.shape[1] // 3 // heads
+    if not lib.htrvt_attn_dropout_supported(N, hd, dt(qkv.dtype)) and N % 8:
+        raise ValueError(f"self_attention: the batched-GEMM route needs N={N} to be a multiple of 8")
+    return _SelfAttention.apply(qkv, B, N, heads, _drop(dropout_p, seed, qkv.device))
+
+
+class _ResidualDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, rows_per_sample, seeds, p, p_path):
+        ctx.args = (rows_per_sample, seeds, p, p_path)
+        return seq_ops.residual_dropout(x.contiguous(), res.contiguous(), *ctx.args)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        return seq_ops.residual_dropout(dy, None, *ctx.args), dy, None, None, None, None
+
+
+def residual_dropout(x, res, B, p, p_path, seeds=None):
+    """res + drop_path(dropout(x, p), p_path) of a block's residual branch in one pass: x, res [B*N, D] (float32 or
+    bfloat16, D a multiple of 4 / 8); element i of x is kept by keep_elem(seeds[0], i), the whole branch of sample b by
+    keep_elem(seeds[1], b), kept values are scaled by 1 / (1 - p) / (1 - p_path).  seeds: int64 device tensor of two
+    elements, None: drawn on the device.  Differentiable in x and res; the backward regenerates both masks."""
+    _need_device(x, res)
+    if x.shape != res.shape or x.dtype != res.dtype or x.dim() != 2 or x.shape[0] % B:
+        raise ValueError("residual_dropout: x and res [B*N, D] of one dtype expected")
+    for q in (p, p_path):
+        if not 0.0 <= float(q) < 1.0:
+            raise ValueError(f"dropout probability {q} outside [0, 1)")
+    if seeds is None and (p > 0 or p_path > 0):
+        seeds = torch.randint(0, 2 ** 62, (2,), dtype=torch.int64, device=x.device)
+    if seeds is not None and (seeds.dtype != torch.int64 or seeds.numel() != 2 or not seeds.is_cuda):
+        raise TypeError("seeds: an int64 device tensor of two elements expected")
+    return _ResidualDropout.apply(x, res, x.shape[0] // B, seeds, float(p), float(p_path))
 
 
 class _CrossAttention(torch.autograd.Function):

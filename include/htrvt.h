@@ -310,6 +310,35 @@ int htrvt_attn_relpos_bwd(const void* qkv, const float* table, const void* out, 
                           float* delta, void* dqkv, float* dtable, float* workspace, int B, int N, int heads, int hd,
                           float scale, int num_patches, int window, int shift, int dtype, void* stream);
 
+/* Dropout on the attention probabilities inside the fused kernels, and the regularisers of a residual branch.
+ * The mask is a pure function of a seed (an int64 on the device, as for htrvt_sgm_dropout) and the element's logical index:
+ *   keep(b, head, q, k) = keep_elem(seed[0], ((b heads + head) N + q) N + k, thr(p))
+ * -- what htrvt_sgm_dropout draws on a dense [B*heads][N][N] tensor with the same seed and p, so the batched-GEMM route
+ * gets the same mask by applying it to P (forward) and dP (backward).  out = (softmax(S) * keep / (1 - p)) v; lse2 is that
+ * of the undropped softmax.  The backward regenerates the mask: nothing but the seed is kept.
+ * p in [0, 1), else an error.  p == 0 is htrvt_attn_fwd/_bwd (bias NULL) resp. htrvt_attn_relpos_fwd/_bwd, bitwise, and seed
+ * may then be NULL.  htrvt_attn_dropout_*: the plain scores (no bias); _supported as htrvt_attn_supported.
+ * htrvt_attn_relpos_dropout_*: the table scores, shapes as htrvt_attn_relpos_supported.
+ * htrvt_residual_dropout: x, res, y [n / D][D] (dtype float32 / bfloat16, D a multiple of 4 / 8), sample b = row /
+ *   rows_per_sample, seeds int64[2] on the device:
+ *     y = res + x * keep_elem(seeds[0], i, thr(p)) / (1 - p) * keep_elem(seeds[1], b, thr(p_path)) / (1 - p_path)
+ *   (element-wise dropout, then drop-path of the whole sample, then the residual add).  res NULL: without the add -- the
+ *   backward, dx from dy.  Either probability may be 0; seeds may be NULL when both are. */
+int htrvt_attn_dropout_supported(int N, int hd, int dtype);
+int htrvt_attn_dropout_fwd(const void* qkv, void* out, float* lse2, int B, int N, int heads, int hd, float scale,
+                           const int64_t* seed, float p, int dtype, void* stream);
+int htrvt_attn_dropout_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, float* delta, void* dqkv,
+                           int B, int N, int heads, int hd, float scale, const int64_t* seed, float p, int dtype, void* stream);
+int htrvt_attn_relpos_dropout_fwd(const void* qkv, const float* table, void* out, float* lse2, int B, int N, int heads, int hd,
+                                  float scale, int num_patches, int window, int shift, const int64_t* seed, float p, int dtype,
+                                  void* stream);
+int htrvt_attn_relpos_dropout_bwd(const void* qkv, const float* table, const void* out, const void* dout, const float* lse2,
+                                  float* delta, void* dqkv, float* dtable, float* workspace, int B, int N, int heads, int hd,
+                                  float scale, int num_patches, int window, int shift, const int64_t* seed, float p, int dtype,
+                                  void* stream);
+int htrvt_residual_dropout(const void* x, const void* res, void* y, int rows_per_sample, int64_t n, int D, const int64_t* seeds,
+                           float p, float p_path, int dtype, void* stream);
+
 /* ---- weight layout helpers ----------------------------------------------------- */
 /* w [Co][Ci][taps] float32 -> fwd [Co][taps][cpad_in], dgrad [Ci][taps][cpad_out] (may be NULL); pads untouched */
 int htrvt_pack_conv_weight(const float* w, void* fwd, void* dgrad, int Co, int Ci, int taps, int cpad_in,

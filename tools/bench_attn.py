@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time the fused attention kernels (csrc/attention.hip) at the model shapes, A/B in one process.
-    python tools/bench_attn.py"""
+    python tools/bench_attn.py
+    python tools/bench_attn.py --drop 0.05      what dropout on the probabilities costs: p = 0 and p interleaved"""
+import argparse
 import os
 import sys
 
@@ -47,5 +49,52 @@ def run():
         print(f"B={B} N={N} h={h} hd={hd}: fwd {res[0]} | bwd(dq+dkv, 7 products) {res[1]}", flush=True)
 
 
+def run_drop(p, rounds):
+    """forward and backward at p = 0 (htrvt_attn_fwd/_bwd) and at p (htrvt_attn_dropout_*), `rounds` interleaved timings of
+    20 launches each: the spread of the p = 0 rounds is the tool's run-to-run noise"""
+    import torch
+    import htrvt_amd  # noqa: F401
+    from htrvt_amd import seq_ops as S
+    for B, N, h, hd in [(128, 256, 6, 128), (128, 128, 6, 128)]:
+        D = h * hd
+        qkv = (torch.randn(B * N, 3 * D, device="cuda") * 1.2).bfloat16()
+        dout = torch.randn(B * N, D, device="cuda").bfloat16()
+        seed = torch.tensor([12345], dtype=torch.int64, device="cuda")
+        state = {}
+
+        def fwd(drop):
+            state[drop is None] = S.attention_fwd(qkv, B, N, h, drop=drop)
+
+        def bwd(drop):
+            out, lse = state[drop is None]
+            S.attention_bwd(qkv, out, dout, lse, B, N, h, drop=drop)
+
+        times = {}
+        for _ in range(rounds):
+            for fn in (fwd, bwd):
+                for drop in (None, (seed, p)):
+                    for _ in range(3):
+                        fn(drop)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        fn(drop)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times.setdefault((fn.__name__, 0.0 if drop is None else p), []).append(e0.elapsed_time(e1) / 20 * 1e3)
+        for (name, q), ts in times.items():
+            ts = sorted(ts)
+            print(f"B={B} N={N} h={h} hd={hd} {name} p={q}: median {ts[len(ts) // 2]:7.1f} us, min {ts[0]:7.1f}, max {ts[-1]:7.1f} "
+                  f"over {rounds} rounds (host allocation included)", flush=True)
+
+
 if __name__ == "__main__":
-    run()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--drop", type=float, default=0.0)
+    ap.add_argument("--rounds", type=int, default=7)
+    args = ap.parse_args()
+    if args.drop > 0:
+        run_drop(args.drop, args.rounds)
+    else:
+        run()
