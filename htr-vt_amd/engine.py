@@ -12,10 +12,12 @@ statistics, logits, parameters and parameter gradients are float32.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import ops, seq_ops
-from ._lib import lib, check, RelayoutJob, RELAYOUT_PACK_CONV, RELAYOUT_CAST_TRANSPOSE, RELAYOUT_UNPACK_WGRAD, RELAYOUT_ARG_JOBS
+from ._lib import lib, check, GemmDesc, RelayoutJob, RELAYOUT_PACK_CONV, RELAYOUT_CAST_TRANSPOSE, RELAYOUT_UNPACK_WGRAD, RELAYOUT_ARG_JOBS
 from .ops import KMAJOR, MNMAJOR, GATHER_CONV_DGRAD, GATHER_CONV_FWD, GATHER_CONV_WGRAD, ConvGeom, cpad, dt, gemm, ptr, stream
 
 LN_EPS = 1e-6       # HTR_VT.py:252
@@ -40,8 +42,17 @@ def stem_tokens(H, W):
     return h * w
 
 
+# Linear layers of one encoder block per block kind, in the model's named_modules() order (the v1 names whatever attention
+# sits between qkv and proj).  A new kind of block is one entry here and one forward / backward pair in Engine._BLOCK.
+_V1_LINEARS = ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")
+BLOCK_LINEARS = {"full": _V1_LINEARS, "relpos": _V1_LINEARS, "local": _V1_LINEARS,
+                 "lgp": ("local_attn.qkv", "local_attn.proj", "global_attn.qkv", "global_attn.proj", "fuse", "mlp.fc1", "mlp.fc2")}
+
+
 class ModelShape:
-    """Static shape of one model (mirrors MaskedAutoencoderViT.__init__, HTR_VT.py:143-172)."""
+    """Static shape of one model (mirrors MaskedAutoencoderViT.__init__, HTR_VT.py:143-172).  `blocks` states the encoder's
+    block list once: per block (kind, arg) = ("full", None), ("relpos", (window, shift)), ("local", (window, shift)) or
+    ("lgp", (window, g_tokens, branch_eps)); `relpos` / `local` / `lgp` stay as attributes for the drop-ins and tools."""
 
     def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS,
                  pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False, lgp=None, pos_table=None,
@@ -97,6 +108,15 @@ class ModelShape:
             self.num_patches = stem_tokens(self.H, self.W)
             self.table_patches = int(table_patches if table_patches is not None else self.num_patches)
             assert self.num_patches <= self.table_patches
+        if self.lgp is not None:
+            self.blocks = [("lgp", self.lgp)] * self.depth
+        elif self.local is not None:      # a None entry of either list is the v1 block
+            self.blocks = [("full", None) if g is None else ("local", g) for g in self.local]
+        elif self.relpos is not None:
+            self.blocks = [("full", None) if g is None else ("relpos", g) for g in self.relpos]
+        else:
+            self.blocks = [("full", None)] * self.depth
+        self.kinds = frozenset(kind for kind, _ in self.blocks)
 
     def stem_convs(self):
         """(param prefix, Ci, Co, k, stride, pad) of every MFMA conv in execution order (resnet18.py:52-71)."""
@@ -113,12 +133,8 @@ class ModelShape:
         return out
 
     def linears(self):
-        names = []
-        attn = ["attn.qkv", "attn.proj"] if self.lgp is None else ["local_attn.qkv", "local_attn.proj", "global_attn.qkv",
-                                                                  "global_attn.proj", "fuse"]
-        for i in range(self.depth):
-            names += [f"blocks.{i}.{n}" for n in attn + ["mlp.fc1", "mlp.fc2"]]
-        return names + ["head"]
+        """parameter prefix of every Linear the engine runs, in the model's named_modules() order"""
+        return [f"blocks.{i}.{n}" for i, (kind, _) in enumerate(self.blocks) for n in BLOCK_LINEARS[kind]] + ["head"]
 
 
 def _job(kind, src, dst0, dst1, d0, d1, taps=0, cpad_in=0, cpad_out=0, row_taps=0, tap0=0):
@@ -140,11 +156,9 @@ class Engine:
         # accumulate).  `gdt` is the element type the big GEMMs' operands have.
         self.split = bool(split_bf16)
         assert not self.split or dtype == torch.float32, "split_bf16 is a mode of the float32 path"
-        if self.split and shape.lgp is not None:
-            raise NotImplementedError("split_bf16 is not served for the LGP blocks: use torch.float32 (parity) or torch.bfloat16")
-        if self.split and shape.local is not None:
-            raise NotImplementedError("split_bf16 is not served for local window blocks: use torch.float32 (parity) or "
-                                      "torch.bfloat16")
+        for kind, what in (("lgp", "the LGP blocks"), ("local", "local window blocks")):
+            if self.split and kind in shape.kinds:
+                raise NotImplementedError(f"split_bf16 is not served for {what}: use torch.float32 (parity) or torch.bfloat16")
         self.gdt = torch.bfloat16 if self.split else dtype
         self._split_cache = []       # backward: the few most recent (source tensor, cat, hi, lo) splits (a gradient feeds dgrad AND wgrad)
         self._saved_planes, self._saving = {}, False    # forward(save=True): id(activation) -> its hi / lo planes, for the weight gradients
@@ -397,8 +411,8 @@ class Engine:
             return out
         if out is None:
             out = self._empty(M, N, dtype=torch.float32 if c_f32 else self.dtype)
-        gemm(x, w, out, dtype=self.dtype, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, bias=bias, act=act, preact=preact,
-             residual=residual, c_f32=c_f32)
+        gemm(x, w, out, dtype=self.dtype, M=M, N=N, K=K, lda=K, ldb=K, ldc=out.stride(0), bias=bias, act=act, preact=preact,
+             residual=residual, c_f32=c_f32)      # (out may be a column block of a wider row-major tensor)
         return out
 
     def linear_dgrad(self, dy, w, wt=None, act=0, preact=None, plain=False, cols=None):
@@ -434,8 +448,6 @@ class Engine:
         eligibility test htrvt_gemm applies), or None where the generic kernel serves the convolution"""
         if self.gdt != torch.bfloat16:
             return None
-        import ctypes
-        from ._lib import GemmDesc
         d = GemmDesc()
         cp = cpad(g.Ci, self.gdt)
         d.dtype, d.a_layout, d.b_layout, d.gather = dt(self.gdt), MNMAJOR, MNMAJOR, GATHER_CONV_WGRAD
@@ -535,8 +547,6 @@ class Engine:
         if self.gdt == torch.bfloat16 and self.deterministic and not plain:
             # the MN-major 8-phase kernel's 256 x 256 tiles where the LIBRARY says it serves the launch (htrvt_gemm_wgrad_tiling:
             # gemm8pt_serves -- alignment, 2 GiB; no copy of that test here)
-            import ctypes
-            from ._lib import GemmDesc
             d = GemmDesc()
             d.dtype, d.a_layout, d.b_layout, d.gather = dt(self.gdt), MNMAJOR, MNMAJOR, 0
             d.M, d.N, d.K, d.lda, d.ldb, d.ldc = N, K, M, (3 * N if self.split else ld), K, K
@@ -608,8 +618,6 @@ class Engine:
         in ONE launch on halo-staged tiles (csrc/gemm_halo_impl.h, gemm_halo_s2_kernel) instead of one gather launch per class"""
         if not (self.gdt == torch.bfloat16 and not self.split and self._dgrad_by_class(g) and g.kh == 3):
             return 0
-        import ctypes
-        from ._lib import GemmDesc
         d = GemmDesc()
         cpo = cpad(g.Co, self.dtype)
         d.dtype, d.a_layout, d.b_layout, d.gather = dt(self.dtype), KMAJOR, KMAJOR, GATHER_CONV_DGRAD
@@ -889,11 +897,11 @@ class Engine:
         return dx, gout
 
     # ------------------------------------------------------------------ LayerNorm pieces
-    def ln_fwd(self, x, gamma, beta, save):
-        return seq_ops.layernorm_fwd(x, gamma, beta, self.s.ln_eps, save)
+    def ln_fwd(self, P, name, x, save):
+        return seq_ops.layernorm_fwd(x, P[name + ".weight"], P[name + ".bias"], self.s.ln_eps, save)
 
-    def ln_bwd(self, dy, x, mean, rstd, gamma, dres, dgamma, dbeta):
-        return seq_ops.layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres)
+    def ln_bwd(self, P, G, name, dy, x, mean, rstd, dres):
+        return seq_ops.layernorm_bwd(dy, x, mean, rstd, P[name + ".weight"], G[name + ".weight"], G[name + ".bias"], dres)
 
     # ------------------------------------------------------------------ forward
     def forward(self, P, img, keep_mask=None, train=False, save=False, want_features=False):
@@ -901,11 +909,28 @@ class Engine:
         img: [B,1,H,W] float32.  keep_mask: None or float32 [N] (1 keep / 0 mask-token).
         Returns float32 logits [B,N,nb_cls] (after the final param-free LayerNorm); want_features: (logits, feats) with
         feats the final norm's output as a fresh float32 [B,N,D] tensor (the SGM forks' feature tap)."""
+        B, u8, keep = self._begin_forward(img, keep_mask, train, want_features)
+        sv = {} if save else None
+        self._split_cache = []
+        self._saved_planes, self._saving = {}, bool(save) and self.split
+        prefetched = self._prefetch_weights(P, save)
+        x, Hc, Wc = self._stem_fwd(P, img, u8, train, save, sv, prefetched)
+        tok, N = self._tokens_fwd(P, x, keep, B, Hc, Wc, sv)
+        xt, enc_saved = self._encoder_fwd(P, tok.view(B * N, self.s.D), B, N, save)
+        y, feats = self._head_fwd(P, xt, B, N, train, sv, want_features)
+        self._saving = False
+        if save:
+            sv["enc"] = enc_saved
+            self.saved = sv
+        return (y, feats) if want_features else y
+
+    def _begin_forward(self, img, keep_mask, train, want_features):
+        """argument checks, the host run-ahead throttle and the upload of the span mask: (B, uint8 pixels?, keep on the device)"""
         s = self.s
         if want_features and self.split:
             raise NotImplementedError("split_bf16 has no feature output: use compute_dtype=torch.float32 (parity) or "
                                       "torch.bfloat16")
-        if want_features and s.lgp is not None:
+        if want_features and "lgp" in s.kinds:
             raise NotImplementedError("want_features is not served for the LGP model")
         if train and s.dropout:
             raise NotImplementedError("train-mode forward of a model with dropout / drop-path: not implemented (build the "
@@ -928,21 +953,17 @@ class Engine:
                 self._call_started.synchronize()
             self._call_started = torch.cuda.Event()
             self._call_started.record()
-        st = stream()
-        sv = {} if save else None
-        self._split_cache = []
-        self._saved_planes, self._saving = {}, bool(save) and self.split
-        C1 = s.D // 4
         keep = None
         if keep_mask is not None:   # uploaded before anything is enqueued: a pageable host->device copy waits for the stream
             keep = keep_mask.to(dtype=torch.float32).contiguous()
             if not keep.is_cuda:    # through pinned memory: a pageable copy would make the host wait for the previous step
                 keep = keep.pin_memory().to(self.dev, non_blocking=True)
+        return B, u8, keep
 
-        # training steps rewrite every weight: re-pack / re-cast all of them on the side stream at the start of the forward,
-        # under the (HBM-bound) image statistics, conv1 and max-pool kernels, instead of ~30 latency-bound launches in
-        # front of their first use
-        prefetched = False
+    def _prefetch_weights(self, P, save):
+        """training steps rewrite every weight: re-pack / re-cast all of them on the side stream at the start of the forward,
+        under the (HBM-bound) image statistics, conv1 and max-pool kernels, instead of ~30 latency-bound launches in
+        front of their first use.  True when the side stream has work the stem must wait for."""
         if self.dtype == torch.bfloat16 and self.single_stream:
             self._repack_all(P, save) if self.table_relayout else None
         elif self.dtype == torch.bfloat16:
@@ -953,19 +974,25 @@ class Engine:
                 if self.table_relayout:
                     self._repack_all(P, save)
                 else:
-                    for name, _ci, _co, _k, _st, _pd in s.stem_convs():
+                    for name, _ci, _co, _k, _st, _pd in self.s.stem_convs():
                         self._conv_w(name, P[name + ".weight"])
                     if save:
                         for li in (1, 2, 3):
                             pb = f"patch_embed.layer{li}.0"
                             self._conv_w_joint_dgrad(pb + ".conv1", P[pb + ".conv1.weight"], pb + ".downsample.0", P[pb + ".downsample.0.weight"])
-                    for name in s.linears():
+                    for name in self.s.linears():
                         if name == "head":
                             self._head_w(P["head.weight"])
                         else:
                             self._lin_w(name, P[name + ".weight"])
-            prefetched = True
+            return True
+        return False
 
+    def _stem_fwd(self, P, img, u8, train, save, sv, prefetched):
+        """the ResNet18 stem up to the layer-3 output: (x [B,Hc,Wc,D], Hc, Wc)"""
+        s, st = self.s, stream()
+        B, _, H, W = img.shape
+        C1 = s.D // 4
         # --- whitening statistics + conv1 + BN + ReLU + maxpool (resnet18.py:74-77) ---
         stats = self._empty(B, 2, dtype=torch.float32)
         check(lib.htrvt_img_stats(ptr(img), ptr(stats), B, H * W, WHITEN_EPS, u8, st), "img_stats")
@@ -1054,8 +1081,13 @@ class Engine:
                                              bn_d=bn_d, out=out, mask=omask))
                 x = out
                 Hc, Wc, Cin = g1.Ho, g1.Wo, planes
+        if save:
+            sv["stem_blocks"] = blocks_saved
+        return x, Hc, Wc
 
-        # --- final maxpool + span mask + pos-embed -> tokens (resnet18.py:82, HTR_VT.py:226-231) ---
+    def _tokens_fwd(self, P, x, keep, B, Hc, Wc, sv):
+        """final maxpool + span mask + pos-embed -> tokens (resnet18.py:82, HTR_VT.py:226-231): (tok [B,N,D], N)"""
+        s, st = self.s, stream()
         Ht = (Hc - 1) // 2 + 1
         N = Ht * Wc
         assert N == s.num_patches, f"token count {N} != num_patches {s.num_patches}"
@@ -1073,40 +1105,23 @@ class Engine:
             pos = self._zero_pos
         check(lib.htrvt_pool_tokens(ptr(x), ptr(keep), ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D, self.dti, st),
               "pool_tokens")
-        if save:
-            sv["stem_blocks"], sv["l3"], sv["keep"], sv["l3_shape"] = blocks_saved, x, keep, (B, Hc, Wc)
+        if sv is not None:
+            sv["l3"], sv["keep"], sv["l3_shape"] = x, keep, (B, Hc, Wc)
+        return tok, N
 
-        # --- transformer blocks (HTR_VT.py:80-83, 27-39) ---
-        M = B * N
-        xt = tok.view(M, D)
+    def _encoder_fwd(self, P, xt, B, N, save):
+        """transformer blocks (HTR_VT.py:80-83), each through the forward of its kind: (output, what the backwards keep)"""
         enc_saved = []
-        for i in range(s.depth):
-            p = f"blocks.{i}"
-            if s.lgp is not None:
-                e, xt = self._lgp_block_fwd(P, p, xt, B, N, save)
-                if save:
-                    enc_saved.append(e)
-                continue
-            ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
-            wq, _ = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
-            qkv = self.linear_fwd(ln1, wq, P[p + ".attn.qkv.bias"])
-            geo = s.relpos[i] if s.relpos is not None else None
-            loc = s.local[i] if s.local is not None else None
-            if geo is not None:
-                O, Pm, lse = self._relpos_attention_fwd(P, p, geo, qkv, B, N, save)
-            elif loc is not None:   # LocalBlock1D: nothing but qkv and O is kept, the backward recomputes the windows' softmax
-                O, Pm, lse = seq_ops.local_attention_fwd(qkv, P[p + ".attn.qkv.bias"], B, N, s.heads, *loc), None, None
-            else:
-                O, Pm, lse = self._attention_fwd(qkv, B, N, save)
-            wp, _ = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
-            x1 = self.linear_fwd(O, wp, P[p + ".attn.proj.bias"], residual=xt)
-            x2, mlp = self._mlp_fwd(P, p, x1, save)
-            if save:
-                enc_saved.append(dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, P=Pm, lse=lse, O=O, x1=x1, geo=geo, loc=loc, **mlp))
-            xt = x2
+        for i, (kind, arg) in enumerate(self.s.blocks):
+            e, xt = self._BLOCK[kind][0](self, P, f"blocks.{i}", kind, arg, xt, B, N, save)
+            enc_saved.append(e)
+        return xt, enc_saved
 
-        # --- norm + head + sequence LayerNorm (HTR_VT.py:236-239) ---
-        xn, mn, rn = self.ln_fwd(xt, P["norm.weight"], P["norm.bias"], save)
+    def _head_fwd(self, P, xt, B, N, train, sv, want_features):
+        """norm + head + sequence LayerNorm (HTR_VT.py:236-239): (logits, feature tap or None)"""
+        s, st = self.s, stream()
+        M, D, save = B * N, s.D, sv is not None
+        xn, mn, rn = self.ln_fwd(P, "norm", xt, save)
         wh, _ = self._head_w(P["head.weight"])
         raw = self._empty(M, s.nb_cls, dtype=torch.float32)
         gemm(xn, wh, raw, dtype=self.dtype, M=M, N=s.nb_cls, K=D, lda=D, ldb=D, ldc=s.nb_cls, bias=P["head.bias"], c_f32=True)
@@ -1116,154 +1131,162 @@ class Engine:
             check(lib.htrvt_seq_whiten_fwd(ptr(raw), ptr(y), ptr(sstats), B, N * s.nb_cls, WHITEN_EPS, 0, st), "seq_whiten_fwd")
         else:                       # window fork: head(norm(x)) is the output (no LayerNorm of the logits)
             y, sstats = raw.view(B, N, s.nb_cls), None
-        self._saving = False
         if save:
-            sv.update(enc=enc_saved, x_last=xt, xn=xn, mn=mn, rn=rn, y=y, sstats=sstats, B=B, N=N, train=train)
-            self.saved = sv
+            sv.update(x_last=xt, xn=xn, mn=mn, rn=rn, y=y, sstats=sstats, B=B, N=N, train=train)
+        feats = None
         if want_features:       # a copy: xn is kept for the head's weight gradient and must not be written by the caller
             feats = torch.empty(B, N, D, dtype=torch.float32, device=self.dev)
             check(lib.htrvt_sgm_convert(ptr(xn), self.dti, ptr(feats), 0, M * D, 0, st), "sgm_convert")
-            return y, feats
-        return y
+        return y, feats
 
-    def _attention_fwd(self, qkv, B, N, save):
-        """full self-attention over N tokens: (O, P or None, lse or None), P / lse as the backward wants them"""
-        h = self.s.heads
-        if self.fused_attention and lib.htrvt_attn_supported(N, self.s.hd, self.dti):
+    # ------------------------------------------------------------------ a Linear's launch sequences, said once
+    def _lin_fwd(self, P, name, x, act=0, preact=None, residual=None, out=None):
+        """y = act(x @ W^T + b) [+ residual] of the Linear `name`"""
+        w, _ = self._lin_w(name, P[name + ".weight"])
+        return self.linear_fwd(x, w, P[name + ".bias"], out=out, act=act, preact=preact, residual=residual)
+
+    def _lin_bwd(self, P, G, name, dy, x, act=0, preact=None, cols=None):
+        """backward of the Linear `name` with input x: returns dx (optionally * gelu'(preact)); the weight and bias gradients
+        go into G on the weight-gradient stream.  cols = (first, N): dy is that column block of a wider tensor."""
+        w, wt = self._lin_w(name, P[name + ".weight"])
+        dx = self.linear_dgrad(dy, w, wt, act=act, preact=preact, cols=cols)
+        self.linear_wgrad(dy, x, G[name + ".weight"], G[name + ".bias"], cols=cols)
+        return dx
+
+    # ------------------------------------------------------------------ attention: the qkv Linear + the scores of one kind
+    def _attn_fwd(self, P, pa, kind, arg, x, B, N, save):
+        """the attention module `pa` up to its projection: qkv = Linear(x), then attention of `kind` over N tokens per image.
+        Returns (qkv, O, (P, lse)): the probabilities or the log-sum-exp, whichever the route's backward reads, else None."""
+        s = self.s
+        h = s.heads
+        qkv = self._lin_fwd(P, pa + ".qkv", x)
+        if kind == "local":     # inside windows of arg = (window, shift) (csrc/lgp.hip; padding slots = the qkv bias, no mask
+            # across the wrap): nothing but qkv and O is kept, the backward recomputes the windows' softmax
+            return qkv, seq_ops.local_attention_fwd(qkv, P[pa + ".qkv.bias"], B, N, h, *arg), (None, None)
+        bias = None
+        if kind == "relpos":    # the block's relative-position table, arg = (window, shift), on the scores
+            tab, tp = P[pa + ".relative_position_bias_table"], s.table_patches
+            if self.dtype == torch.bfloat16:    # the table-driven fused kernels (csrc/attn_relpos.hip)
+                if not lib.htrvt_attn_relpos_supported(N, s.hd, self.dti, tp, *arg):
+                    raise RuntimeError(f"{pa}: relative-position attention: {lib.htrvt_last_error().decode()}")
+                O, lse = seq_ops.relpos_attention_fwd(qkv, tab, B, N, h, tp, *arg, save=save)
+                return qkv, O, (None, lse)
+            assert not self.split, "split_bf16: no relative-position attention"
+            bias = seq_ops.relpos_bias_fwd(tab, N, tp, *arg, N)     # float32: a dense bias into the batched-GEMM route
+        elif self.fused_attention and lib.htrvt_attn_supported(N, s.hd, self.dti):
             # bf16: one launch, scores / probabilities stay on chip; lse is what the recomputing backward needs
             O, lse = seq_ops.attention_fwd(qkv, B, N, h, save=save)
-            return O, None, lse
-        return (*seq_ops.attention_unfused_fwd(qkv, B, N, h), None)
+            return qkv, O, (None, lse)
+        O, Pm = seq_ops.attention_unfused_fwd(qkv, B, N, h, bias=bias)
+        return qkv, O, (Pm, None)
 
-    def _attention_bwd(self, qkv, Pm, lse, O, dO, B, N):
-        if Pm is None:      # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
-            return seq_ops.attention_bwd(qkv, O, dO, lse, B, N, self.s.heads)
-        return seq_ops.attention_unfused_bwd(qkv, Pm, dO, B, N, self.s.heads)
+    def _attn_bwd(self, P, G, pa, kind, arg, x, qkv, O, kept, dO, B, N):
+        """backward of _attn_fwd: the gradient of x.  The qkv Linear's gradients and the relative-position table's are ADDED
+        to G (every route is reproducible: fixed-order sums, no atomics)."""
+        s = self.s
+        h = s.heads
+        Pm, lse = kept
+        if kind == "local":
+            dqkv, dpad = seq_ops.local_attention_bwd(qkv, P[pa + ".qkv.bias"], dO, B, N, h, *arg)
+        elif kind == "relpos":
+            name, tp = pa + ".relative_position_bias_table", s.table_patches
+            gt = G.get(name)
+            if Pm is None:
+                dqkv = seq_ops.relpos_attention_bwd(qkv, P[name], O, dO, lse, B, N, h, tp, *arg, dtable=gt)
+            else:
+                dbias = torch.zeros(h, N, N, dtype=torch.float32, device=self.dev)
+                dqkv = seq_ops.attention_unfused_bwd(qkv, Pm, dO, B, N, h, dbias=dbias)
+                if gt is not None:
+                    dtab = seq_ops.relpos_bias_bwd(dbias, N, tp, *arg)
+                    check(lib.htrvt_rowsum_f32(ptr(dtab), 1, dtab.numel(), ptr(gt), stream()), "rowsum")
+        elif Pm is None:        # fused forward: recomputing fused backward (dQ launch, then dK/dV launch)
+            dqkv = seq_ops.attention_bwd(qkv, O, dO, lse, B, N, h)
+        else:
+            dqkv = seq_ops.attention_unfused_bwd(qkv, Pm, dO, B, N, h)
+        dx = self._lin_bwd(P, G, pa + ".qkv", dqkv, x)
+        if kind == "local" and N % arg[0]:
+            # ragged last window: its padding slots hold the qkv bias, so their k / v gradient belongs to the k / v thirds of
+            # the bias gradient; on the weight-gradient stream, behind the bias column sum of the Linear above
+            D, gb = s.D, G[pa + ".qkv.bias"]
+            self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, gb.data_ptr() + 4 * D, dti=0), dpad)
+        return dx
 
+    # ------------------------------------------------------------------ the blocks, one forward / backward pair per kind
     def _mlp_fwd(self, P, p, x1, save):
         """x2 = x1 + fc2(gelu(fc1(norm2(x1)))); returns (x2, what the backward keeps)"""
-        ln2, m2, r2 = self.ln_fwd(x1, P[p + ".norm2.weight"], P[p + ".norm2.bias"], save)
-        w1_, _ = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
+        ln2, m2, r2 = self.ln_fwd(P, p + ".norm2", x1, save)
         hpre = self._empty(x1.shape[0], self.s.hidden) if save else None
-        hact = self.linear_fwd(ln2, w1_, P[p + ".mlp.fc1.bias"], act=1, preact=hpre)
-        w2_, _ = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
-        x2 = self.linear_fwd(hact, w2_, P[p + ".mlp.fc2.bias"], residual=x1)
+        hact = self._lin_fwd(P, p + ".mlp.fc1", ln2, act=1, preact=hpre)
+        x2 = self._lin_fwd(P, p + ".mlp.fc2", hact, residual=x1)
         return x2, dict(ln2=ln2, m2=m2, r2=r2, hpre=hpre, h=hact)
 
     def _mlp_bwd(self, P, G, e, dx):
         """gradient of the block's x1 (MLP branch + residual) from the gradient of its output"""
         p = e["p"]
-        w2_, w2t = self._lin_w(p + ".mlp.fc2", P[p + ".mlp.fc2.weight"])
-        dhpre = self.linear_dgrad(dx, w2_, w2t, act=2, preact=e["hpre"])
-        self.linear_wgrad(dx, e["h"], G[p + ".mlp.fc2.weight"], G[p + ".mlp.fc2.bias"])
-        w1_, w1t = self._lin_w(p + ".mlp.fc1", P[p + ".mlp.fc1.weight"])
-        dln2 = self.linear_dgrad(dhpre, w1_, w1t)
-        self.linear_wgrad(dhpre, e["ln2"], G[p + ".mlp.fc1.weight"], G[p + ".mlp.fc1.bias"])
+        dhpre = self._lin_bwd(P, G, p + ".mlp.fc2", dx, e["h"], act=2, preact=e["hpre"])
+        dln2 = self._lin_bwd(P, G, p + ".mlp.fc1", dhpre, e["ln2"])
         del dhpre
-        return self.ln_bwd(dln2, e["x1"], e["m2"], e["r2"], P[p + ".norm2.weight"], dx, G[p + ".norm2.weight"],
-                           G[p + ".norm2.bias"])
+        return self.ln_bwd(P, G, p + ".norm2", dln2, e["x1"], e["m2"], e["r2"], dx)
 
-    # ------------------------------------------------------------------ the LGP fork's block (model_lgp/model/plg.py:172-212)
-    def _lgp_block_fwd(self, P, p, xt, B, N, save):
-        """x1 = x + fuse([local_attn(y) | global_attn(y)]), y = norm1(x); x2 = x1 + mlp(norm2(x1)).  The two branches write
-        the halves of one [B N][2D] buffer (no cat copy); csrc/lgp.hip has the window attention, the pooling + LayerNorm in
-        front of the global branch and the scaled up-sampling behind it, everything else is the kernels of the v1 block."""
-        s = self.s
-        D, h, M = s.D, s.heads, B * N
-        win, gtok, beps = s.lgp
+    def _v1_block_fwd(self, P, p, kind, arg, xt, B, N, save):
+        """the v1-shaped block (HTR_VT.py:27-39) with the attention of `kind` ("full", "relpos" or "local"):
+        x1 = x + proj(attention(norm1(x))); x2 = x1 + mlp(norm2(x1)).  Returns (what the backward keeps or None, x2)."""
+        ln1, m1, r1 = self.ln_fwd(P, p + ".norm1", xt, save)
+        qkv, O, kept = self._attn_fwd(P, p + ".attn", kind, arg, ln1, B, N, save)
+        x1 = self._lin_fwd(P, p + ".attn.proj", O, residual=xt)
+        x2, mlp = self._mlp_fwd(P, p, x1, save)
+        e = dict(kind=kind, arg=arg, p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, O=O, attn=kept, x1=x1, **mlp) if save else None
+        return e, x2
+
+    def _v1_block_bwd(self, P, G, e, dx, B, N):
+        p = e["p"]
+        dx1 = self._mlp_bwd(P, G, e, dx)                                  # MLP: x2 = x1 + fc2(gelu(fc1(ln2)))
+        dO = self._lin_bwd(P, G, p + ".attn.proj", dx1, e["O"])           # attention: x1 = x0 + proj(attn(ln1))
+        dln1 = self._attn_bwd(P, G, p + ".attn", e["kind"], e["arg"], e["ln1"], e["qkv"], e["O"], e["attn"], dO, B, N)
+        return self.ln_bwd(P, G, p + ".norm1", dln1, e["x0"], e["m1"], e["r1"], dx1)
+
+    def _lgp_block_fwd(self, P, p, kind, arg, xt, B, N, save):
+        """the LGP fork's block (model_lgp/model/plg.py:172-212): x1 = x + fuse([local_attn(y) | global_attn(y)]), y = norm1(x);
+        x2 = x1 + mlp(norm2(x1)).  The two branches write the halves of one [B N][2D] buffer (no cat copy); csrc/lgp.hip has
+        the window attention, the pooling + LayerNorm in front of the global branch and the scaled up-sampling behind it,
+        everything else is the kernels of the v1 block."""
+        D, M = self.s.D, B * N
+        win, gtok, beps = arg
         Gt = min(gtok, N)
-        ln1, m1, r1 = self.ln_fwd(xt, P[p + ".norm1.weight"], P[p + ".norm1.bias"], save)
+        ln1, m1, r1 = self.ln_fwd(P, p + ".norm1", xt, save)
         cat = self._empty(M, 2 * D)
         # local branch: qkv -> attention inside windows (padding slots = the qkv bias) -> proj into the left half
-        lb = P[p + ".local_attn.qkv.bias"]
-        wq, _ = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
-        qkv = self.linear_fwd(ln1, wq, lb)
-        O = seq_ops.local_attention_fwd(qkv, lb, B, N, h, win)
-        wp, _ = self._lin_w(p + ".local_attn.proj", P[p + ".local_attn.proj.weight"])
-        gemm(O, wp, cat, dtype=self.dtype, M=M, N=D, K=D, lda=D, ldb=D, ldc=2 * D, bias=P[p + ".local_attn.proj.bias"])
+        qkv, O, kept = self._attn_fwd(P, p + ".local_attn", "local", (win, 0), ln1, B, N, save)
+        self._lin_fwd(P, p + ".local_attn.proj", O, out=cat[:, :D])
         # global branch: pool to Gt tokens + LayerNorm -> qkv -> full attention -> proj -> up-sample * sigmoid(alpha), right half
         z, _, zrstd = seq_ops.pool_norm_fwd(ln1, B, N, Gt, beps)
-        wgq, _ = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
-        qkvg = self.linear_fwd(z, wgq, P[p + ".global_attn.qkv.bias"])
-        Og, Pg, lseg = self._attention_fwd(qkvg, B, Gt, save)
-        wgp, _ = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
-        yg = self.linear_fwd(Og, wgp, P[p + ".global_attn.proj.bias"])
+        qkvg, Og, keptg = self._attn_fwd(P, p + ".global_attn", "full", None, z, B, Gt, save)
+        yg = self._lin_fwd(P, p + ".global_attn.proj", Og)
         seq_ops.upsample_fwd(yg, P[p + ".global_attn.logit_alpha"], cat[:, D:], B, N, Gt)
-        wf, _ = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
-        x1 = self.linear_fwd(cat, wf, P[p + ".fuse.bias"], residual=xt)
+        x1 = self._lin_fwd(P, p + ".fuse", cat, residual=xt)
         x2, mlp = self._mlp_fwd(P, p, x1, save)
-        e = None
-        if save:
-            e = dict(p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, O=O, cat=cat, z=z, zrstd=zrstd, qkvg=qkvg, Pg=Pg, lseg=lseg,
-                     Og=Og, yg=yg, x1=x1, Gt=Gt, **mlp)
+        e = dict(kind=kind, p=p, x0=xt, ln1=ln1, m1=m1, r1=r1, qkv=qkv, O=O, attn=kept, cat=cat, z=z, zrstd=zrstd, qkvg=qkvg,
+                 attng=keptg, Og=Og, yg=yg, x1=x1, win=win, Gt=Gt, **mlp) if save else None
         return e, x2
 
     def _lgp_block_bwd(self, P, G, e, dx, B, N):
-        s = self.s
-        D, h = s.D, s.heads
-        win, Gt = s.lgp[0], e["Gt"]
-        p = e["p"]
+        D, p, win, Gt = self.s.D, e["p"], e["win"], e["Gt"]
         dx1 = self._mlp_bwd(P, G, e, dx)
-        wf, wft = self._lin_w(p + ".fuse", P[p + ".fuse.weight"])
-        dcat = self.linear_dgrad(dx1, wf, wft)                       # [M][2D]: left half d local proj, right half d global
-        self.linear_wgrad(dx1, e["cat"], G[p + ".fuse.weight"], G[p + ".fuse.bias"])
+        dcat = self._lin_bwd(P, G, p + ".fuse", dx1, e["cat"])       # [M][2D]: left half d local proj, right half d global
         # global branch
         dyg = seq_ops.upsample_bwd(dcat[:, D:], e["yg"], P[p + ".global_attn.logit_alpha"], G[p + ".global_attn.logit_alpha"],
                                    B, N, Gt)
-        wgp, wgpt = self._lin_w(p + ".global_attn.proj", P[p + ".global_attn.proj.weight"])
-        dOg = self.linear_dgrad(dyg, wgp, wgpt)
-        self.linear_wgrad(dyg, e["Og"], G[p + ".global_attn.proj.weight"], G[p + ".global_attn.proj.bias"])
-        dqkvg = self._attention_bwd(e["qkvg"], e["Pg"], e["lseg"], e["Og"], dOg, B, Gt)
-        wgq, wgqt = self._lin_w(p + ".global_attn.qkv", P[p + ".global_attn.qkv.weight"])
-        dz = self.linear_dgrad(dqkvg, wgq, wgqt)
-        self.linear_wgrad(dqkvg, e["z"], G[p + ".global_attn.qkv.weight"], G[p + ".global_attn.qkv.bias"])
+        dOg = self._lin_bwd(P, G, p + ".global_attn.proj", dyg, e["Og"])
+        dz = self._attn_bwd(P, G, p + ".global_attn", "full", None, e["z"], e["qkvg"], e["Og"], e["attng"], dOg, B, Gt)
         # local branch
-        wp, wpt = self._lin_w(p + ".local_attn.proj", P[p + ".local_attn.proj.weight"])
-        dO = self.linear_dgrad(dcat, wp, wpt, cols=(0, D))
-        self.linear_wgrad(dcat, e["O"], G[p + ".local_attn.proj.weight"], G[p + ".local_attn.proj.bias"], cols=(0, D))
-        lb, glb = P[p + ".local_attn.qkv.bias"], G[p + ".local_attn.qkv.bias"]
-        dqkv, dpad = seq_ops.local_attention_bwd(e["qkv"], lb, dO, B, N, h, win)
-        wq, wqt = self._lin_w(p + ".local_attn.qkv", P[p + ".local_attn.qkv.weight"])
-        dln1 = self.linear_dgrad(dqkv, wq, wqt)
-        self.linear_wgrad(dqkv, e["ln1"], G[p + ".local_attn.qkv.weight"], glb)
-        if N % win:     # the padding rows' k / v gradient; on the weight-gradient stream, behind the bias column sum above
-            self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, glb.data_ptr() + 4 * D, dti=0), dpad)
+        dO = self._lin_bwd(P, G, p + ".local_attn.proj", dcat, e["O"], cols=(0, D))
+        dln1 = self._attn_bwd(P, G, p + ".local_attn", "local", (win, 0), e["ln1"], e["qkv"], e["O"], e["attn"], dO, B, N)
         seq_ops.pool_norm_bwd(dz, e["z"], e["zrstd"], B, N, Gt, dx=dln1)      # added to the local branch's gradient
-        return self.ln_bwd(dln1, e["x0"], e["m1"], e["r1"], P[p + ".norm1.weight"], dx1, G[p + ".norm1.weight"],
-                           G[p + ".norm1.bias"])
+        return self.ln_bwd(P, G, p + ".norm1", dln1, e["x0"], e["m1"], e["r1"], dx1)
 
-    def _relpos_attention_fwd(self, P, p, geo, qkv, B, N, save):
-        """attention of a window-fork block with its relative-position table: bf16 on the table-driven fused kernels
-        (csrc/attn_relpos.hip), float32 through the dense bias + the batched-GEMM route; (O, P or None, lse or None)"""
-        s = self.s
-        h, tp = s.heads, s.table_patches
-        ws, shift = geo
-        tab = P[p + ".attn.relative_position_bias_table"]
-        if self.dtype == torch.bfloat16:
-            if not lib.htrvt_attn_relpos_supported(N, s.hd, self.dti, tp, ws, shift):
-                raise RuntimeError(f"{p}: relative-position attention: {lib.htrvt_last_error().decode()}")
-            O, lse = seq_ops.relpos_attention_fwd(qkv, tab, B, N, h, tp, ws, shift, save=save)
-            return O, None, lse
-        assert not self.split, "split_bf16: no relative-position attention"
-        bias = seq_ops.relpos_bias_fwd(tab, N, tp, ws, shift, N)
-        return (*seq_ops.attention_unfused_fwd(qkv, B, N, h, bias=bias), None)
-
-    def _relpos_attention_bwd(self, P, G, e, dO, B, N):
-        """backward of _relpos_attention_fwd; the table gradient is ADDED to G (both routes are reproducible: fixed-order
-        sums, no atomics)"""
-        s = self.s
-        h, tp = s.heads, s.table_patches
-        ws, shift = e["geo"]
-        name = e["p"] + ".attn.relative_position_bias_table"
-        tab, gt = P[name], G.get(name)
-        if e["P"] is None:
-            return seq_ops.relpos_attention_bwd(e["qkv"], tab, e["O"], dO, e["lse"], B, N, h, tp, ws, shift, dtable=gt)
-        dbias = torch.zeros(h, N, N, dtype=torch.float32, device=self.dev)
-        dqkv = seq_ops.attention_unfused_bwd(e["qkv"], e["P"], dO, B, N, h, dbias=dbias)
-        if gt is not None:
-            dtab = seq_ops.relpos_bias_bwd(dbias, N, tp, ws, shift)
-            check(lib.htrvt_rowsum_f32(ptr(dtab), 1, dtab.numel(), ptr(gt), stream()), "rowsum")
-        return dqkv
+    # block kind -> (forward, backward); ModelShape.blocks says which kind each block is
+    _BLOCK = {"full": (_v1_block_fwd, _v1_block_bwd), "relpos": (_v1_block_fwd, _v1_block_bwd),
+              "local": (_v1_block_fwd, _v1_block_bwd), "lgp": (_lgp_block_fwd, _lgp_block_bwd)}
 
     # ------------------------------------------------------------------ backward
     def backward(self, P, G, dy, after_encoder=None, after_layer3=None, dfeats=None):
@@ -1273,11 +1296,9 @@ class Engine:
         forward(save=True)."""
         sv = self.saved
         assert sv is not None, "backward() needs forward(..., save=True)"
-        s = self.s
-        st = stream()
-        B, N, D = sv["B"], sv["N"], s.D
+        s, st = self.s, stream()
+        B, N, D, C = sv["B"], sv["N"], s.D, s.nb_cls
         M = B * N
-        C = s.nb_cls
         assert dy is not None or dfeats is not None, "backward() needs dy and / or dfeats"
         if dfeats is not None:
             dfeats = dfeats.contiguous()
@@ -1293,12 +1314,20 @@ class Engine:
             dxn = self._head_backward(P, G, sv, dy.contiguous(), B, N, M, C, D, st)
             if dfeats is not None:
                 check(lib.htrvt_sgm_convert(ptr(dfeats), 0, ptr(dxn), self.dti, M * D, 1, st), "sgm_convert")
-        self._encoder_backward(P, G, sv, dxn, after_encoder, after_layer3)
+        dx = self._encoder_bwd(P, G, sv, dxn, B, N, after_encoder)
+        dfeat = self._tokens_bwd(G, sv, dx, B, N)
+        self._stem_bwd(P, G, sv, dfeat, B, after_layer3)
+        self._flush_unpacks()
+        self._join_side()
+        self._side_active = False
+        self._zarena_end()
+        self._split_cache = []
+        self._saved_planes = {}
+        self.saved = None
 
     def _head_backward(self, P, G, sv, dy, B, N, M, C, D, st):
         s = self.s
         assert dy.dtype == torch.float32 and dy.shape == (B, N, C)
-
         # sequence LN, head, final norm
         Cp = (C + 7) // 8 * 8           # class dim padded so that every 16-byte chunk is aligned
         if s.whiten_logits:
@@ -1325,44 +1354,18 @@ class Engine:
             check(lib.htrvt_rowsum_f32(ptr(dbp), 1, C, ptr(G["head.bias"]), st), "rowsum")
         return dxn
 
-    def _encoder_backward(self, P, G, sv, dxn, after_encoder, after_layer3):
-        s = self.s
-        st = stream()
-        B, N, D = sv["B"], sv["N"], s.D
-        M = B * N
-        dx = self.ln_bwd(dxn, sv["x_last"], sv["mn"], sv["rn"], P["norm.weight"], None, G["norm.weight"], G["norm.bias"])
-
+    def _encoder_bwd(self, P, G, sv, dxn, B, N, after_encoder):
+        """final norm and the encoder blocks, last to first, each through the backward of its kind: the gradient of the tokens"""
+        dx = self.ln_bwd(P, G, "norm", dxn, sv["x_last"], sv["mn"], sv["rn"], None)
         for e in reversed(sv["enc"]):
-            p = e["p"]
-            if s.lgp is not None:
-                dx = self._lgp_block_bwd(P, G, e, dx, B, N)
-                continue
-            # MLP: x2 = x1 + fc2(gelu(fc1(ln2)))
-            dx1 = self._mlp_bwd(P, G, e, dx)
-            # attention: x1 = x0 + proj(attn(ln1))
-            wp, wpt = self._lin_w(p + ".attn.proj", P[p + ".attn.proj.weight"])
-            dO = self.linear_dgrad(dx1, wp, wpt)
-            self.linear_wgrad(dx1, e["O"], G[p + ".attn.proj.weight"], G[p + ".attn.proj.bias"])
-            dpad = None
-            if e.get("geo") is not None:
-                dqkv = self._relpos_attention_bwd(P, G, e, dO, B, N)
-            elif e.get("loc") is not None:
-                dqkv, dpad = seq_ops.local_attention_bwd(e["qkv"], P[p + ".attn.qkv.bias"], dO, B, N, s.heads, *e["loc"])
-            else:
-                dqkv = self._attention_bwd(e["qkv"], e["P"], e["lse"], e["O"], dO, B, N)
-            wq, wqt = self._lin_w(p + ".attn.qkv", P[p + ".attn.qkv.weight"])
-            dln1 = self.linear_dgrad(dqkv, wq, wqt)
-            gqb = G[p + ".attn.qkv.bias"]
-            self.linear_wgrad(dqkv, e["ln1"], G[p + ".attn.qkv.weight"], gqb)
-            if dpad is not None and N % e["loc"][0]:    # the padding rows' k / v gradient, as in _lgp_block_bwd
-                self._on_side(lambda: ops.colsum(dpad, B, 2 * D, 2 * D, gqb.data_ptr() + 4 * D, dti=0), dpad)
-            dx = self.ln_bwd(dln1, e["x0"], e["m1"], e["r1"], P[p + ".norm1.weight"], dx1, G[p + ".norm1.weight"],
-                             G[p + ".norm1.bias"])
-
+            dx = self._BLOCK[e["kind"]][1](self, P, G, e, dx, B, N)
         if after_encoder is not None:   # every blocks.*, norm, head gradient is enqueued: DP bucket can go
             after_encoder(self._wgrad_stream())      # (the collective waits for the weight-gradient stream, not this one)
+        return dx
 
-        # token assembly
+    def _tokens_bwd(self, G, sv, dx, B, N):
+        """token assembly: the mask token's gradient and the gradient of the layer-3 output"""
+        st, M, D = stream(), B * N, self.s.D
         keep = sv["keep"]
         if keep is not None:
             ops.colsum(dx, M, D, D, G["mask_token"], dti=self.dti, keep=keep, keep_mod=N)
@@ -1370,7 +1373,11 @@ class Engine:
         dfeat = self._empty(Bq, Hc, Wc, D)
         check(lib.htrvt_pool_tokens_bwd(ptr(dx), ptr(sv["l3"]), ptr(keep), ptr(dfeat), B, Hc, N, D, self.dti, st),
               "pool_tokens_bwd")
+        return dfeat
 
+    def _stem_bwd(self, P, G, sv, dfeat, B, after_layer3):
+        """residual stages, last block to first, then the first max-pool + bn1 + conv1"""
+        st = stream()
         # residual stages.  bf16: the ReLU mask of a block's output and the BatchNorm-backward sums of its bn2 (and
         # downsample BN) are produced by the epilogue of the dgrad GEMM that creates that gradient; float32 (parity
         # path) keeps the separate reduction pass.
@@ -1478,7 +1485,6 @@ class Engine:
             else:
                 dout = self.conv_dgrad(dca, wd1, blk["g1"], residual=gm, **kw)
 
-        # first maxpool + bn1 + conv1
         img, c1 = sv["img"], sv["c1"]
         u8 = 1 if img.dtype == torch.uint8 else 0
         sc, sf, mean, rstd = sv["bn1"]
@@ -1500,10 +1506,3 @@ class Engine:
             partial = self._empty(nblk, C1 * 9, dtype=torch.float32)
             check(lib.htrvt_conv1_wgrad(ptr(img), ptr(sv["stats"]), ptr(dc1), ptr(G["patch_embed.conv1.weight"]), ptr(partial),
                                         B, 2 * Hh, W, C1, self.dti, u8, st), "conv1_wgrad")
-        self._flush_unpacks()
-        self._join_side()
-        self._side_active = False
-        self._zarena_end()
-        self._split_cache = []
-        self._saved_planes = {}
-        self.saved = None

@@ -173,7 +173,7 @@ class Trainer:
         batches).  Call after at least one eager step() of the same batch shape (lazily sized workspaces, one-time
         kernel attributes and the engine's streams exist then).  Returns a GraphedStep; its step() has step()'s
         signature and results (bit-identical: same kernels, same order, same scalars)."""
-        if getattr(self.engine.s, "lgp", None) is not None:
+        if "lgp" in self.engine.s.kinds:
             raise NotImplementedError("Trainer.capture_step is not served for the LGP model: use step()")
         return GraphedStep(self, img, max_target_len, masked, single_stream)
 

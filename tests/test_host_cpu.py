@@ -98,6 +98,9 @@ def test_create_model_matches_reference_init(golden_dir):
     assert np.array_equal(sums, g["sums"]) and np.array_equal(abss, g["abssums"])   # same RNG stream, same bits
     assert sum(p.numel() for p in m.parameters()) == int(g["nparams"]) == 53486096
     assert m.embed_dim == 768 and m.num_patches == 128
+    assert m._shape.blocks == [("full", None)] * 4
+    assert len(m._shape.linears()) == 17 and m._shape.linears() == [n for n, mod in m.named_modules()
+                                   if isinstance(mod, torch.nn.Linear) and (n.startswith("blocks.") or n == "head")]
     assert not m.pos_embed.requires_grad and m.mask_token.requires_grad
     with pytest.raises(TypeError):                     # duplicate kwargs fail exactly as in the reference
         HTR_VT.create_model(80, [64, 512], embed_dim=256)

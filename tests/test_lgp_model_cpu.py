@@ -35,6 +35,9 @@ def test_lgp_state_dict_matches_reference_init(golden_dir):
     assert a.dim() == 0 and abs(float(a) - float(np.log(0.4 / 0.6))) < 1e-6
     assert m.blocks[0].global_attn.branch_norm.eps == 1e-5 and m.blocks[0].norm1.eps == 1e-6
     assert m._shape.lgp == (12, 64, 1e-5) and m._shape.num_patches == 128
+    assert m._shape.blocks == [("lgp", (12, 64, 1e-5))] * 4
+    assert len(m._shape.linears()) == 29 and m._shape.linears() == [n for n, mod in m.named_modules()
+                                   if isinstance(mod, torch.nn.Linear) and (n.startswith("blocks.") or n == "head")]
     assert m._shape.linears()[:7] == ["blocks.0." + n for n in ("local_attn.qkv", "local_attn.proj", "global_attn.qkv",
                                                                  "global_attn.proj", "fuse", "mlp.fc1", "mlp.fc2")]
 

@@ -79,6 +79,9 @@ def test_sgm_encoder_state_dict_is_model_v1s():
     assert list(a.keys()) == list(b.keys())
     assert all(torch.equal(a[k], b[k]) for k in a)
     assert isinstance(m, V1.MaskedAutoencoderViT) and hasattr(m, "forward_features")
+    assert m._shape.blocks == [("full", None)] * 4
+    assert len(m._shape.linears()) == 17 and m._shape.linears() == [n for n, mod in m.named_modules()
+                                   if isinstance(mod, torch.nn.Linear) and (n.startswith("blocks.") or n == "head")]
 
 
 def test_sgm_refuses_cpu_tensors():

@@ -45,6 +45,9 @@ def test_slg_block_kinds_and_shape():
     assert type(m.blocks[1].attn) is M.WindowMHSA1D and type(m.blocks[2].attn) is M.Attention
     assert (m.blocks[0].attn.shift, m.blocks[1].attn.shift, m.blocks[1].attn.win) == (0, 6, 12)
     assert m._shape.relpos is None and m._shape.lgp is None and m._shape.num_patches == 128
+    assert m._shape.blocks == [("local", (12, 0)), ("local", (12, 6)), ("full", None), ("full", None)]
+    assert len(m._shape.linears()) == 17 and m._shape.linears() == [n for n, mod in m.named_modules()
+                                   if isinstance(mod, torch.nn.Linear) and (n.startswith("blocks.") or n == "head")]
     assert m._shape.linears()[:4] == ["blocks.0." + n for n in ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")]
     for W, patch in SC.TINY.items():        # the tiny geometries of the fixture: the table has as many rows as the stem leaves
         t = M.MaskedAutoencoderViT(SC.NB_CLS, img_size=[64, W], patch_size=patch, **SC.TINY_KW)

@@ -33,6 +33,16 @@ def test_window_state_dict_matches_reference_init(golden_dir):
     assert idx.dtype == torch.int64 and idx.shape == (128, 128) and int(idx[0, 127]) == 254 and int(idx[127, 0]) == 0
     assert torch.all(sd["blocks.0.attn.relative_position_bias_table"] == 0)
     assert [(b.window_size, b.shift_size) for b in m.blocks] == [(16, 0), (16, 8), (0, 0), (0, 0)]
+    assert m._shape.blocks == [("relpos", (16, 0)), ("relpos", (16, 8)), ("relpos", (0, 0)), ("relpos", (0, 0))]
+    assert len(m._shape.linears()) == 17 and m._shape.linears() == [n for n, mod in m.named_modules()
+                                   if isinstance(mod, torch.nn.Linear) and (n.startswith("blocks.") or n == "head")]
+
+
+def test_model_shape_relpos_none_is_the_full_attention_block():
+    from htrvt_amd.engine import ModelShape
+    s = ModelShape(80, (64, 512), 768, 4, 6, pos_embed=False, whiten_logits=False, relpos=[(16, 0), None, (0, 0), None])
+    assert s.blocks == [("relpos", (16, 0)), ("full", None), ("relpos", (0, 0)), ("full", None)]
+    assert s.relpos == [(16, 0), None, (0, 0), None] and len(s.linears()) == 17
 
 
 def test_window_create_model_rejects_unknown_kwargs():
