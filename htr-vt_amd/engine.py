@@ -13,6 +13,7 @@ statistics, logits, parameters and parameter gradients are float32.
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 
 import torch
 
@@ -47,6 +48,21 @@ def stem_tokens(H, W):
 _V1_LINEARS = ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")
 BLOCK_LINEARS = {"full": _V1_LINEARS, "relpos": _V1_LINEARS, "local": _V1_LINEARS,
                  "lgp": ("local_attn.qkv", "local_attn.proj", "global_attn.qkv", "global_attn.proj", "fuse", "mlp.fc1", "mlp.fc2")}
+
+# The stem plan's records.  StemBlock: one residual block (ModelShape.stem_blocks), conv1 has the stride.  BNCoeffs: the
+# per-channel float32 vectors of one BatchNorm application, y = x * scale + shift; mean / rstd are what its backward reads.
+# SavedBN: one application as its backward needs it: coefficients, parameter prefix, the tensor it normalised.
+# ResBlockSaved: what a block's forward keeps: prefix, input x, a1 = relu(bn1(conv1 out)), the output and its 1-bit ReLU
+# mask (or None); ConvGeom and SavedBN of conv1 (g1, bn_a), conv2 (g2, bn_b) and the downsample (gd, bn_d; None without one).
+# StemGrad: the gradient of a block's output on its way to that block's backward: raw (sums None), or already g = dOut *
+# (out > 0) with sums = [(partial, rows)] of the block's bn2 [and downsample BN] from the epilogue of the dgrad that made it.
+StemBlock = namedtuple("StemBlock", "prefix Cin planes stride downsample")
+BNCoeffs = namedtuple("BNCoeffs", "scale shift mean rstd")
+SavedBN = namedtuple("SavedBN", "coef prefix x")
+class ResBlockSaved(namedtuple("ResBlockSaved", "p x g1 bn_a a1 g2 bn_b gd bn_d out mask")):
+    __slots__ = ()
+    __getitem__ = lambda self, name: getattr(self, name)     # by field name, blk["x"]: how the tests and tools read it
+StemGrad = namedtuple("StemGrad", "g sums", defaults=(None,))
 
 
 class ModelShape:
@@ -118,18 +134,24 @@ class ModelShape:
             self.blocks = [("full", None)] * self.depth
         self.kinds = frozenset(kind for kind, _ in self.blocks)
 
-    def stem_convs(self):
-        """(param prefix, Ci, Co, k, stride, pad) of every MFMA conv in execution order (resnet18.py:52-71)."""
+    def stem_blocks(self):
+        """the stem's residual blocks in execution order (resnet18.py:52-71): two per stage, the first strided and with a
+        1x1 downsample conv + BatchNorm on the residual"""
         D = self.D
         out, inpl = [], D // 4
         for li, (planes, stride) in enumerate(((D // 4, (2, 1)), (D // 2, (2, 2)), (D, (2, 2))), start=1):
-            p = f"patch_embed.layer{li}"
-            out.append((f"{p}.0.conv1", inpl, planes, 3, stride, 1))
-            out.append((f"{p}.0.conv2", planes, planes, 3, (1, 1), 1))
-            out.append((f"{p}.0.downsample.0", inpl, planes, 1, stride, 0))
-            out.append((f"{p}.1.conv1", planes, planes, 3, (1, 1), 1))
-            out.append((f"{p}.1.conv2", planes, planes, 3, (1, 1), 1))
+            out.append(StemBlock(f"patch_embed.layer{li}.0", inpl, planes, stride, True))
+            out.append(StemBlock(f"patch_embed.layer{li}.1", planes, planes, (1, 1), False))
             inpl = planes
+        return out
+
+    def stem_convs(self):
+        """(param prefix, Ci, Co, k, stride, pad) of every MFMA conv in execution order."""
+        out = []
+        for b in self.stem_blocks():
+            out += [(b.prefix + ".conv1", b.Cin, b.planes, 3, b.stride, 1), (b.prefix + ".conv2", b.planes, b.planes, 3, (1, 1), 1)]
+            if b.downsample:
+                out.append((b.prefix + ".downsample.0", b.Cin, b.planes, 1, b.stride, 0))
         return out
 
     def linears(self):
@@ -147,6 +169,7 @@ def _job(kind, src, dst0, dst1, d0, d1, taps=0, cpad_in=0, cpad_out=0, row_taps=
 class Engine:
     def __init__(self, shape: ModelShape, dtype=torch.float32, device="cuda", split_bf16=False):
         self.s = shape
+        self._stem_blocks, self._stem_convs = shape.stem_blocks(), shape.stem_convs()     # read every step: made once
         self.dtype = dtype
         self.dev = torch.device(device)
         self.dti = dt(dtype)
@@ -198,6 +221,7 @@ class Engine:
         self.saved = None
         self._bn_train = True
         self._zarena, self._zoff, self._zneed, self._zneed_max = None, None, 0, 0
+        self._pos_table, self._zero_pos = None, None     # device copies of the position table the tokens get (_tokens_fwd)
 
     # ------------------------------------------------------------------ small helpers
     def _empty(self, *shape, dtype=None):
@@ -638,8 +662,8 @@ class Engine:
         if nm > 0:
             return nm
         if self._dgrad_by_class(g):
-            return sum(ops.gemm_num_mtiles(g.B * ((g.Hi - a + g.sh - 1) // g.sh) * ((g.Wi - b + g.sw - 1) // g.sw), g.Ci,
-                                           self.dtype, gather=GATHER_CONV_DGRAD) for a in range(g.sh) for b in range(g.sw))
+            return sum(ops.gemm_num_mtiles(g.B * Hq * Wq, g.Ci, self.dtype, gather=GATHER_CONV_DGRAD)
+                       for _a, _b, _nt, Hq, Wq in g.parity_classes())
         return ops.gemm_num_mtiles(g.B * g.Hi * g.Wi, g.Ci, self.dtype, gather=GATHER_CONV_DGRAD)
 
     def _dgrad_by_class(self, g):
@@ -663,20 +687,16 @@ class Engine:
             cp3 = cpad(3 * g.Co, self.gdt)
             g3 = ConvGeom(g.B, g.Hi, g.Wi, g.Ci, 3 * g.Co, g.kh, (g.sh, g.sw), g.ph)
             parts = {}
-            for a in range(g.sh):
-                for b in range(g.sw):
-                    nt = sum(1 for dy_ in range(g.kh) if (a + g.ph - dy_) % g.sh == 0) * \
-                         sum(1 for dx_ in range(g.kw) if (b + g.pw - dx_) % g.sw == 0)
-                    Hq, Wq = (g.Hi - a + g.sh - 1) // g.sh, (g.Wi - b + g.sw - 1) // g.sw
-                    if nt == 0:      # no tap reaches this class (1x1 strided conv): its gradient is zero
-                        parts[(a, b)] = torch.zeros(g.B, Hq, Wq, g.Ci, dtype=torch.float32, device=self.dev)
-                        continue
-                    part = self._empty(g.B, Hq, Wq, g.Ci)
-                    # cls selects the taps and the gathered pixels; with cls the float32 epilogue writes row m of the class
-                    # at row m of C: a dense matrix
-                    gemm(dy3, wd, part, dtype=self.gdt, M=g.B * Hq * Wq, N=g.Ci, K=nt * cp3, lda=3 * g.Co, ldb=g.taps * cp3, ldc=g.Ci,
-                         gather=GATHER_CONV_DGRAD, geom=g3, Cpad=cp3, cls=(a, b), c_f32=True)
-                    parts[(a, b)] = part
+            for a, b, nt, Hq, Wq in g.parity_classes():
+                if nt == 0:      # no tap reaches this class (1x1 strided conv): its gradient is zero
+                    parts[(a, b)] = torch.zeros(g.B, Hq, Wq, g.Ci, dtype=torch.float32, device=self.dev)
+                    continue
+                part = self._empty(g.B, Hq, Wq, g.Ci)
+                # cls selects the taps and the gathered pixels; with cls the float32 epilogue writes row m of the class
+                # at row m of C: a dense matrix
+                gemm(dy3, wd, part, dtype=self.gdt, M=g.B * Hq * Wq, N=g.Ci, K=nt * cp3, lda=3 * g.Co, ldb=g.taps * cp3, ldc=g.Ci,
+                     gather=GATHER_CONV_DGRAD, geom=g3, Cpad=cp3, cls=(a, b), c_f32=True)
+                parts[(a, b)] = part
             check(lib.htrvt_class_scatter_f32(ptr(parts[(0, 0)]), ptr(parts.get((0, 1))), ptr(parts.get((1, 0))), ptr(parts.get((1, 1))),
                                               ptr(residual), ptr(dx), g.B, g.Hi, g.Wi, g.Ci, g.sh, g.sw, stream()), "class_scatter_f32")
             return dx
@@ -694,22 +714,18 @@ class Engine:
             if par and self._cls_streams is None:
                 self._cls_streams = [torch.cuda.Stream(device=self.dev) for _ in range(3)]
             used = []
-            for a in range(g.sh):
-                for b in range(g.sw):
-                    nt = sum(1 for dy_ in range(g.kh) if (a + g.ph - dy_) % g.sh == 0) * \
-                         sum(1 for dx_ in range(g.kw) if (b + g.pw - dx_) % g.sw == 0)
-                    Hq, Wq = (g.Hi - a + g.sh - 1) // g.sh, (g.Wi - b + g.sw - 1) // g.sw
-                    idx = a * g.sw + b
-                    st_ = self._cls_streams[idx - 1] if (par and idx > 0) else main
-                    if st_ is not main:
-                        st_.wait_stream(main)
-                        used.append(st_)
-                    a2 = extra if (extra is not None and (a, b) == (0, 0)) else None    # the pixels a 1x1 stride-s conv reads
-                    with torch.cuda.stream(st_):
-                        gemm(dy, wd, dx, dtype=self.dtype, M=g.B * Hq * Wq, N=g.Ci, K=(nt + (1 if a2 is not None else 0)) * cpo,
-                             lda=g.Co, ldb=wtaps * cpo, ldc=g.Ci, gather=GATHER_CONV_DGRAD, geom=g, Cpad=cpo, residual=residual,
-                             cls=(a, b), relu_src=relu_src, relu_bits=relu_bits, bnb=bnb, bnb_tile0=tile0, a2=a2)
-                    tile0 += ops.gemm_num_mtiles(g.B * Hq * Wq, g.Ci, self.dtype, gather=GATHER_CONV_DGRAD)
+            for a, b, nt, Hq, Wq in g.parity_classes():
+                idx = a * g.sw + b
+                st_ = self._cls_streams[idx - 1] if (par and idx > 0) else main
+                if st_ is not main:
+                    st_.wait_stream(main)
+                    used.append(st_)
+                a2 = extra if (extra is not None and (a, b) == (0, 0)) else None    # the pixels a 1x1 stride-s conv reads
+                with torch.cuda.stream(st_):
+                    gemm(dy, wd, dx, dtype=self.dtype, M=g.B * Hq * Wq, N=g.Ci, K=(nt + (1 if a2 is not None else 0)) * cpo,
+                         lda=g.Co, ldb=wtaps * cpo, ldc=g.Ci, gather=GATHER_CONV_DGRAD, geom=g, Cpad=cpo, residual=residual,
+                         cls=(a, b), relu_src=relu_src, relu_bits=relu_bits, bnb=bnb, bnb_tile0=tile0, a2=a2)
+                tile0 += ops.gemm_num_mtiles(g.B * Hq * Wq, g.Ci, self.dtype, gather=GATHER_CONV_DGRAD)
             for st_ in used:       # every class has written its pixels before anything downstream reads dx
                 main.wait_stream(st_)
             return dx
@@ -779,7 +795,7 @@ class Engine:
         _head_w would do one tensor at a time on their first use after an optimizer step)."""
         s = self.s
         jobs, fresh = [], []
-        for name, _ci, _co, _k, _st, _pd in s.stem_convs():
+        for name, _ci, _co, _k, _st, _pd in self._stem_convs:
             w = P[name + ".weight"]
             key, ent = self._wkey(w), self._packs.get(name)
             if ent is not None and ent[0] == key:
@@ -790,19 +806,17 @@ class Engine:
                                                    torch.zeros(Ci, taps, cpo, dtype=self.dtype, device=self.dev))
             jobs.append(_job(RELAYOUT_PACK_CONV, w, bufs[0], bufs[1], Co, Ci, taps, cpi, cpo, taps, 0))
             fresh.append((name, key, bufs))
-        if save:
-            for li in (1, 2, 3):
-                pb = f"patch_embed.layer{li}.0"
-                w3, wd = P[pb + ".conv1.weight"], P[pb + ".downsample.0.weight"]
-                key, ent = (self._wkey(w3), self._wkey(wd)), self._packs.get(pb + ".conv1+ds")
-                if ent is not None and ent[0] == key:
-                    continue
-                Co, Ci, kh, kw = w3.shape
-                taps, cpi, cpo = kh * kw, cpad(Ci, self.dtype), cpad(Co, self.dtype)
-                buf = ent[1] if ent is not None else torch.zeros(Ci, taps + 1, cpo, dtype=self.dtype, device=self.dev)
-                jobs.append(_job(RELAYOUT_PACK_CONV, w3, None, buf, Co, Ci, taps, cpi, cpo, taps + 1, 0))
-                jobs.append(_job(RELAYOUT_PACK_CONV, wd, None, buf, Co, Ci, 1, cpi, cpo, taps + 1, taps))
-                fresh.append((pb + ".conv1+ds", key, buf))
+        for pb in (b.prefix for b in self._stem_blocks if save and b.downsample):     # the joint dgrad packs
+            w3, wd = P[pb + ".conv1.weight"], P[pb + ".downsample.0.weight"]
+            key, ent = (self._wkey(w3), self._wkey(wd)), self._packs.get(pb + ".conv1+ds")
+            if ent is not None and ent[0] == key:
+                continue
+            Co, Ci, kh, kw = w3.shape
+            taps, cpi, cpo = kh * kw, cpad(Ci, self.dtype), cpad(Co, self.dtype)
+            buf = ent[1] if ent is not None else torch.zeros(Ci, taps + 1, cpo, dtype=self.dtype, device=self.dev)
+            jobs.append(_job(RELAYOUT_PACK_CONV, w3, None, buf, Co, Ci, taps, cpi, cpo, taps + 1, 0))
+            jobs.append(_job(RELAYOUT_PACK_CONV, wd, None, buf, Co, Ci, 1, cpi, cpo, taps + 1, taps))
+            fresh.append((pb + ".conv1+ds", key, buf))
         for name in s.linears():
             w = P[name + ".weight"]
             key, ent = self._wkey(w), self._packs.get(name)
@@ -825,7 +839,7 @@ class Engine:
 
     # ------------------------------------------------------------------ BatchNorm pieces
     def bn_coeffs(self, P, prefix, C, train, cs=None, rows=0, count=0, save=False):
-        """returns (scale, shift, save_mean, save_rstd)"""
+        """returns BNCoeffs (scale, shift, save_mean, save_rstd)"""
         scale, shift = self._empty(C, dtype=torch.float32), self._empty(C, dtype=torch.float32)
         if train:
             mean, rstd = self._empty(C, dtype=torch.float32), self._empty(C, dtype=torch.float32)
@@ -833,14 +847,14 @@ class Engine:
                                         BN_EPS, BN_MOMENTUM, ptr(P[prefix + ".running_mean"]),
                                         ptr(P[prefix + ".running_var"]), ptr(P[prefix + ".num_batches_tracked"]),
                                         ptr(scale), ptr(shift), ptr(mean), ptr(rstd), stream()), "bn_finalize")
-            return scale, shift, mean, rstd
+            return BNCoeffs(scale, shift, mean, rstd)
         # eval mode (running statistics).  save: an eval-mode backward (frozen-BN fine-tuning, saliency) needs them as
         # (mean, rstd); they are constants there, bn_backward_finish is told so through self._bn_train
         rstd = self._empty(C, dtype=torch.float32) if save else None
         check(lib.htrvt_bn_eval_coeffs(ptr(P[prefix + ".weight"]), ptr(P[prefix + ".bias"]), ptr(P[prefix + ".running_mean"]),
                                        ptr(P[prefix + ".running_var"]), BN_EPS, ptr(scale), ptr(shift), ptr(rstd), C, stream()),
               "bn_eval_coeffs")
-        return scale, shift, (P[prefix + ".running_mean"] if save else None), rstd
+        return BNCoeffs(scale, shift, P[prefix + ".running_mean"] if save else None, rstd)
 
     def bn_apply(self, x, scale, shift, relu, res=None, rscale=None, rshift=None, want_mask=False):
         """y = [relu](x * scale + shift [+ res [* rscale + rshift]]); want_mask: also the 1-bit-per-element sign mask of y
@@ -856,45 +870,49 @@ class Engine:
                                  x.numel() // C, C, 1 if relu else 0, self.dti, stream()), "bn_apply")
         return y
 
-    def bn_backward(self, dy, yact, x, prefix, P, G, mean, rstd, want_g=False, out=None):
-        """dx of train-mode BN (+ReLU mask from yact); accumulates dgamma/dbeta into G.  Unfused form: one
-        reduction pass over (dy, yact, x), then bn_backward_finish."""
-        C = x.shape[-1]
-        npix = x.numel() // C
+    def bn_backward(self, dy, yact, bn, P, G, want_g=False, out=None):
+        """dx of the train-mode BatchNorm `bn` (SavedBN) (+ReLU mask from yact); accumulates dgamma/dbeta into G.  Unfused
+        form: one reduction pass over (dy, yact, x), then bn_backward_finish."""
+        C = bn.x.shape[-1]
+        npix = bn.x.numel() // C
         nblk = lib.htrvt_bn_bwd_blocks(npix)
         partial = self._empty(nblk, 2, C, dtype=torch.float32)
-        check(lib.htrvt_bn_bwd_reduce(ptr(dy), ptr(yact), ptr(x), ptr(mean), ptr(rstd), ptr(partial), npix, C, self.dti,
-                                      stream()), "bn_bwd_reduce")
-        return self.bn_backward_finish(partial, nblk, dy, yact, x, prefix, P, G, mean, rstd, want_g, out=out)
+        check(lib.htrvt_bn_bwd_reduce(ptr(dy), ptr(yact), ptr(bn.x), ptr(bn.coef.mean), ptr(bn.coef.rstd), ptr(partial), npix, C,
+                                      self.dti, stream()), "bn_bwd_reduce")
+        return self.bn_backward_finish(partial, nblk, dy, yact, bn, P, G, want_g, out=out)
 
-    def bn_backward_coef(self, partial, rows, x, prefix, P, G, mean, rstd):
+    def bn_backward_coef(self, partial, rows, bn, P, G):
         """finalize dgamma / dbeta (accumulated into G) and the [3][C] coefficients of dx = cA*g + cB*x + cC from per-tile
         partial sums"""
-        C = x.shape[-1]
-        npix = x.numel() // C
+        C = bn.x.shape[-1]
         coef = self._empty(3, C, dtype=torch.float32)
-        src = partial
         if rows > 64:   # two-level reduction of the partial rows
             red = self._zeros(2 * C)
             ops.colsum(partial, rows, 2 * C, 2 * C, red, dti=0)
-            src, rows = red, 1
-        count = float(npix) if self._bn_train else -1.0      # eval mode: dx = gamma * rstd * g
-        check(lib.htrvt_bn_bwd_finalize(ptr(src), rows, C, count, ptr(P[prefix + ".weight"]), ptr(mean), ptr(rstd),
-                                        ptr(G[prefix + ".weight"]), ptr(G[prefix + ".bias"]), ptr(coef), stream()),
-              "bn_bwd_finalize")
+            partial, rows = red, 1
+        count = float(bn.x.numel() // C) if self._bn_train else -1.0      # eval mode: dx = gamma * rstd * g
+        check(lib.htrvt_bn_bwd_finalize(ptr(partial), rows, C, count, ptr(P[bn.prefix + ".weight"]), ptr(bn.coef.mean),
+                                        ptr(bn.coef.rstd), ptr(G[bn.prefix + ".weight"]), ptr(G[bn.prefix + ".bias"]), ptr(coef),
+                                        stream()), "bn_bwd_finalize")
         return coef
 
-    def bn_backward_finish(self, partial, rows, g, yact, x, prefix, P, G, mean, rstd, want_g=False, out=None):
+    def bn_backward_finish(self, partial, rows, g, yact, bn, P, G, want_g=False, out=None):
         """finalize (dgamma, dbeta, coefficients) from per-tile partial sums, then dx = cA*g + cB*x + cC.
         With yact=None, g is the already ReLU-masked gradient (fused dgrad epilogue)."""
+        x = bn.x
         C = x.shape[-1]
-        npix = x.numel() // C
-        coef = self.bn_backward_coef(partial, rows, x, prefix, P, G, mean, rstd)
+        coef = self.bn_backward_coef(partial, rows, bn, P, G)
         dx = torch.empty_like(x) if out is None else out
         gout = torch.empty_like(x) if want_g else None
-        check(lib.htrvt_bn_bwd_apply(ptr(g), ptr(yact), ptr(x), ptr(coef), ptr(dx), ptr(gout), npix, C, self.dti, stream()),
-              "bn_bwd_apply")
+        check(lib.htrvt_bn_bwd_apply(ptr(g), ptr(yact), ptr(x), ptr(coef), ptr(dx), ptr(gout), x.numel() // C, C, self.dti,
+                                     stream()), "bn_bwd_apply")
         return dx, gout
+
+    def _bnb_request(self, bns, rows):
+        """fused BatchNorm-backward sums of a conv_dgrad with `rows` M tiles, for the BatchNorms `bns` its output gradient
+        feeds: (conv_dgrad's bnb list [(x, mean, rstd, partial)], [(partial [rows, 2, C], rows)])"""
+        bufs = [self._empty(rows, 2, bn.x.shape[-1], dtype=torch.float32) for bn in bns]
+        return [(bn.x, bn.coef.mean, bn.coef.rstd, b) for bn, b in zip(bns, bufs)], [(b, rows) for b in bufs]
 
     # ------------------------------------------------------------------ LayerNorm pieces
     def ln_fwd(self, P, name, x, save):
@@ -965,7 +983,8 @@ class Engine:
         under the (HBM-bound) image statistics, conv1 and max-pool kernels, instead of ~30 latency-bound launches in
         front of their first use.  True when the side stream has work the stem must wait for."""
         if self.dtype == torch.bfloat16 and self.single_stream:
-            self._repack_all(P, save) if self.table_relayout else None
+            if self.table_relayout:
+                self._repack_all(P, save)
         elif self.dtype == torch.bfloat16:
             if self._side is None:
                 self._side = torch.cuda.Stream(device=self.dev)
@@ -974,12 +993,10 @@ class Engine:
                 if self.table_relayout:
                     self._repack_all(P, save)
                 else:
-                    for name, _ci, _co, _k, _st, _pd in self.s.stem_convs():
+                    for name, _ci, _co, _k, _st, _pd in self._stem_convs:
                         self._conv_w(name, P[name + ".weight"])
-                    if save:
-                        for li in (1, 2, 3):
-                            pb = f"patch_embed.layer{li}.0"
-                            self._conv_w_joint_dgrad(pb + ".conv1", P[pb + ".conv1.weight"], pb + ".downsample.0", P[pb + ".downsample.0.weight"])
+                    for pb in (b.prefix for b in self._stem_blocks if save and b.downsample):
+                        self._conv_w_joint_dgrad(pb + ".conv1", P[pb + ".conv1.weight"], pb + ".downsample.0", P[pb + ".downsample.0.weight"])
                     for name in self.s.linears():
                         if name == "head":
                             self._head_w(P["head.weight"])
@@ -990,10 +1007,23 @@ class Engine:
 
     def _stem_fwd(self, P, img, u8, train, save, sv, prefetched):
         """the ResNet18 stem up to the layer-3 output: (x [B,Hc,Wc,D], Hc, Wc)"""
-        s, st = self.s, stream()
+        x = self._stem_head_fwd(P, img, u8, train, save, sv)
+        if prefetched:
+            torch.cuda.current_stream().wait_stream(self._side)
+        # --- residual stages (resnet18.py:79-81, 23-39) ---
+        block_fwd = self._res_block_fwd if (train or save) else self._res_block_fwd_eval
+        blocks_saved = []
+        for b in self._stem_blocks:
+            x, blk = block_fwd(P, b, x, train, save)
+            blocks_saved.append(blk)
+        if save:
+            sv["stem_blocks"] = blocks_saved
+        return x, x.shape[1], x.shape[2]
+
+    def _stem_head_fwd(self, P, img, u8, train, save, sv):
+        """whitening statistics + conv1 + BN + ReLU + maxpool (resnet18.py:74-77): the pooled activations [B,Hp,W,D/4]"""
+        st, C1 = stream(), self.s.D // 4
         B, _, H, W = img.shape
-        C1 = s.D // 4
-        # --- whitening statistics + conv1 + BN + ReLU + maxpool (resnet18.py:74-77) ---
         stats = self._empty(B, 2, dtype=torch.float32)
         check(lib.htrvt_img_stats(ptr(img), ptr(stats), B, H * W, WHITEN_EPS, u8, st), "img_stats")
         w1 = P["patch_embed.conv1.weight"]
@@ -1005,85 +1035,75 @@ class Engine:
         # BatchNorm coming from the image's second moments (csrc/stem.hip: stem_moments / stem_stats / stem_fused_fwd).
         fused_stem = self.fuse_stem_forward and (not save or (train and self.fuse_conv1_backward))
         if fused_stem:
-            c1 = None
+            c1, cs = None, None
             if train:
                 cs = self._empty(2, C1, dtype=torch.float32)
                 part = self._empty(lib.htrvt_stem_stats_rows(B, H), 64, dtype=torch.float32)
                 check(lib.htrvt_stem_stats(ptr(img), ptr(stats), ptr(w1), ptr(part), ptr(cs), B, H, W, C1, u8, st), "stem_stats")
-                sc, sf, mean, rstd = self.bn_coeffs(P, "patch_embed.bn1", C1, True, cs, 1, B * (H // 2) * W, save=save)
-            else:
-                sc, sf, mean, rstd = self.bn_coeffs(P, "patch_embed.bn1", C1, False, save=save)
-            check(lib.htrvt_stem_fwd(ptr(img), ptr(stats), ptr(w1), ptr(sc), ptr(sf), ptr(a), ptr(idx), B, H, W, C1, self.dti,
-                                     u8, st), "stem_fwd")
+            bn = self.bn_coeffs(P, "patch_embed.bn1", C1, train, cs, 1, B * (H // 2) * W, save=save)
+            check(lib.htrvt_stem_fwd(ptr(img), ptr(stats), ptr(w1), ptr(bn.scale), ptr(bn.shift), ptr(a), ptr(idx), B, H, W, C1,
+                                     self.dti, u8, st), "stem_fwd")
         else:
             c1 = self._empty(B, H // 2, W, C1)
             cs = self._empty(B * (H // 2) + 64, 2, C1, dtype=torch.float32) if train else self._empty(B * (H // 2), 2, C1, dtype=torch.float32)
             check(lib.htrvt_conv1_fwd(ptr(img), ptr(stats), ptr(w1), ptr(c1), ptr(cs), B, H, W, C1, self.dti, u8, st), "conv1_fwd")
-            sc, sf, mean, rstd = self.bn_coeffs(P, "patch_embed.bn1", C1, train, cs, B * (H // 2), B * (H // 2) * W, save=save)
-            check(lib.htrvt_bn_relu_maxpool(ptr(c1), ptr(sc), ptr(sf), ptr(a), ptr(idx), B, H // 2, W, C1, self.dti, st),
+            bn = self.bn_coeffs(P, "patch_embed.bn1", C1, train, cs, B * (H // 2), B * (H // 2) * W, save=save)
+            check(lib.htrvt_bn_relu_maxpool(ptr(c1), ptr(bn.scale), ptr(bn.shift), ptr(a), ptr(idx), B, H // 2, W, C1, self.dti, st),
                   "bn_relu_maxpool")
         if save:
-            sv["img"], sv["stats"], sv["c1"], sv["bn1"], sv["idx"] = img, stats, c1, (sc, sf, mean, rstd), idx
-            sv["c1_shape"] = (B, H // 2, W, C1)
+            sv.update(img=img, stats=stats, c1=c1, bn1=bn, idx=idx, c1_shape=(B, H // 2, W, C1))
+        return a
 
-        if prefetched:
-            torch.cuda.current_stream().wait_stream(self._side)
+    def _res_block_geoms(self, b, x):
+        """ConvGeoms of the block `b` (StemBlock) on the input x: (conv1, conv2, downsample or None)"""
+        B, Hc, Wc, _ = x.shape
+        g1 = ConvGeom(B, Hc, Wc, b.Cin, b.planes, 3, b.stride, 1)
+        g2 = ConvGeom(B, g1.Ho, g1.Wo, b.planes, b.planes, 3, (1, 1), 1)
+        return g1, g2, ConvGeom(B, Hc, Wc, b.Cin, b.planes, 1, b.stride, 0) if b.downsample else None
 
-        # --- residual stages (resnet18.py:79-81, 23-39) ---
-        x = a
-        Hc, Wc, Cin = Hp, W, C1
-        blocks_saved = []
-        for li, (planes, stride) in enumerate(((s.D // 4, (2, 1)), (s.D // 2, (2, 2)), (s.D, (2, 2))), start=1):
-            for bi in range(2):
-                p = f"patch_embed.layer{li}.{bi}"
-                strd = stride if bi == 0 else (1, 1)
-                g1 = ConvGeom(B, Hc, Wc, Cin, planes, 3, strd, 1)
-                wf1, _ = self._conv_w(p + ".conv1", P[p + ".conv1.weight"])
-                g2 = ConvGeom(B, g1.Ho, g1.Wo, planes, planes, 3, (1, 1), 1)
-                wf2, _ = self._conv_w(p + ".conv2", P[p + ".conv2.weight"])
-                if not train and not save:
-                    # eval: running statistics are known up front, every BatchNorm (+ residual + ReLU) rides in the
-                    # epilogue of its convolution: 2-3 launches per block, no normalisation passes
-                    bn_a = self.bn_coeffs(P, p + ".bn1", planes, False)
-                    a1, _, _ = self.conv_fwd(x, wf1, g1, False, bn=bn_a, relu=True)
-                    bn_b = self.bn_coeffs(P, p + ".bn2", planes, False)
-                    res = x
-                    if bi == 0:
-                        gd = ConvGeom(B, Hc, Wc, Cin, planes, 1, strd, 0)
-                        wfd, _ = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
-                        bn_d = self.bn_coeffs(P, p + ".downsample.1", planes, False)
-                        res, _, _ = self.conv_fwd(x, wfd, gd, False, bn=bn_d)
-                    out, _, _ = self.conv_fwd(a1, wf2, g2, False, bn=bn_b, relu=True, residual=res)
-                    x = out
-                    Hc, Wc, Cin = g1.Ho, g1.Wo, planes
-                    continue
-                ca, cs1, r1 = self.conv_fwd(x, wf1, g1, train)
-                bn_a = self.bn_coeffs(P, p + ".bn1", planes, train, cs1, r1, B * g1.Ho * g1.Wo, save=save)
-                a1 = self.bn_apply(ca, bn_a[0], bn_a[1], relu=True)
-                cb, cs2, r2 = self.conv_fwd(a1, wf2, g2, train)
-                bn_b = self.bn_coeffs(P, p + ".bn2", planes, train, cs2, r2, B * g2.Ho * g2.Wo, save=save)
-                if bi == 0:
-                    gd = ConvGeom(B, Hc, Wc, Cin, planes, 1, strd, 0)
-                    wfd, _ = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
-                    cd, csd, rd = self.conv_fwd(x, wfd, gd, train)
-                    bn_d = self.bn_coeffs(P, p + ".downsample.1", planes, train, csd, rd, B * gd.Ho * gd.Wo, save=save)
-                    res_kw = dict(res=cd, rscale=bn_d[0], rshift=bn_d[1])
-                else:
-                    gd, cd, bn_d = None, None, None
-                    res_kw = dict(res=x)
-                # the block's output ReLU: the forward BatchNorm pass writes its 1-bit mask, and its backward (fused into the
-                # NEXT block's conv1 dgrad) reads that instead of the activation
-                want_mask = bool(save and self.fuse_bn_backward and self.dtype == torch.bfloat16 and planes % 8 == 0)
-                out = self.bn_apply(cb, bn_b[0], bn_b[1], relu=True, want_mask=want_mask, **res_kw)
-                out, omask = out if want_mask else (out, None)
-                if save:
-                    blocks_saved.append(dict(p=p, x=x, g1=g1, ca=ca, bn_a=bn_a, a1=a1, g2=g2, cb=cb, bn_b=bn_b, gd=gd, cd=cd,
-                                             bn_d=bn_d, out=out, mask=omask))
-                x = out
-                Hc, Wc, Cin = g1.Ho, g1.Wo, planes
-        if save:
-            sv["stem_blocks"] = blocks_saved
-        return x, Hc, Wc
+    def _res_block_fwd_eval(self, P, b, x, train=False, save=False):
+        """one residual block, not train and not save: running statistics are known up front, every BatchNorm (+ residual +
+        ReLU) rides in the epilogue of its convolution: 2-3 launches per block, no normalisation passes.  (out, None)"""
+        p = b.prefix
+        g1, g2, gd = self._res_block_geoms(b, x)
+        wf1, _ = self._conv_w(p + ".conv1", P[p + ".conv1.weight"])
+        wf2, _ = self._conv_w(p + ".conv2", P[p + ".conv2.weight"])
+        a1, _, _ = self.conv_fwd(x, wf1, g1, False, bn=self.bn_coeffs(P, p + ".bn1", b.planes, False), relu=True)
+        bn_b = self.bn_coeffs(P, p + ".bn2", b.planes, False)
+        res = x
+        if gd is not None:
+            wfd, _ = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
+            res, _, _ = self.conv_fwd(x, wfd, gd, False, bn=self.bn_coeffs(P, p + ".downsample.1", b.planes, False))
+        out, _, _ = self.conv_fwd(a1, wf2, g2, False, bn=bn_b, relu=True, residual=res)
+        return out, None
+
+    def _conv_bn(self, P, x, wf, g, prefix, train, save):
+        """raw convolution + the coefficients of the BatchNorm behind it (train: batch statistics from the conv's epilogue)"""
+        c, cs, rows = self.conv_fwd(x, wf, g, train)
+        return SavedBN(self.bn_coeffs(P, prefix, g.Co, train, cs, rows, g.B * g.Ho * g.Wo, save=save), prefix, c)
+
+    def _res_block_fwd(self, P, b, x, train, save):
+        """one residual block with separate BatchNorm passes (train mode, or an eval forward that saves for its backward):
+        (out, ResBlockSaved or None)"""
+        p = b.prefix
+        g1, g2, gd = self._res_block_geoms(b, x)
+        wf1, _ = self._conv_w(p + ".conv1", P[p + ".conv1.weight"])
+        wf2, _ = self._conv_w(p + ".conv2", P[p + ".conv2.weight"])
+        bn_a = self._conv_bn(P, x, wf1, g1, p + ".bn1", train, save)
+        a1 = self.bn_apply(bn_a.x, bn_a.coef.scale, bn_a.coef.shift, relu=True)
+        bn_b = self._conv_bn(P, a1, wf2, g2, p + ".bn2", train, save)
+        if gd is not None:
+            wfd, _ = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
+            bn_d = self._conv_bn(P, x, wfd, gd, p + ".downsample.1", train, save)
+            res_kw = dict(res=bn_d.x, rscale=bn_d.coef.scale, rshift=bn_d.coef.shift)
+        else:
+            bn_d, res_kw = None, dict(res=x)
+        # the block's output ReLU: the forward BatchNorm pass writes its 1-bit mask, and its backward (fused into the
+        # NEXT block's conv1 dgrad) reads that instead of the activation
+        want_mask = bool(save and self.fuse_bn_backward and self.dtype == torch.bfloat16 and b.planes % 8 == 0)
+        out = self.bn_apply(bn_b.x, bn_b.coef.scale, bn_b.coef.shift, relu=True, want_mask=want_mask, **res_kw)
+        out, omask = out if want_mask else (out, None)
+        return out, (ResBlockSaved(p, x, g1, bn_a, a1, g2, bn_b, gd, bn_d, out, omask) if save else None)
 
     def _tokens_fwd(self, P, x, keep, B, Hc, Wc, sv):
         """final maxpool + span mask + pos-embed -> tokens (resnet18.py:82, HTR_VT.py:226-231): (tok [B,N,D], N)"""
@@ -1094,13 +1114,13 @@ class Engine:
         D = s.D
         tok = self._empty(B, N, D)
         if s.pos_table is not None:     # LGP fork: the model's own table (no state-dict entry)
-            if getattr(self, "_pos_table", None) is None:
+            if self._pos_table is None:
                 self._pos_table = s.pos_table.to(self.dev).contiguous()
             pos = self._pos_table
         elif s.pos_embed:
             pos = P["pos_embed"].reshape(N, D)
         else:                       # window fork: no absolute position embedding (HTR_VT.py:265 of model_window)
-            if getattr(self, "_zero_pos", None) is None or self._zero_pos.shape != (N, D):
+            if self._zero_pos is None or self._zero_pos.shape != (N, D):
                 self._zero_pos = torch.zeros(N, D, dtype=torch.float32, device=self.dev)
             pos = self._zero_pos
         check(lib.htrvt_pool_tokens(ptr(x), ptr(keep), ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D, self.dti, st),
@@ -1377,132 +1397,112 @@ class Engine:
 
     def _stem_bwd(self, P, G, sv, dfeat, B, after_layer3):
         """residual stages, last block to first, then the first max-pool + bn1 + conv1"""
-        st = stream()
-        # residual stages.  bf16: the ReLU mask of a block's output and the BatchNorm-backward sums of its bn2 (and
-        # downsample BN) are produced by the epilogue of the dgrad GEMM that creates that gradient; float32 (parity
-        # path) keeps the separate reduction pass.
         blocks = sv["stem_blocks"]
-
-        def can_fuse(g):   # served by the LDS-DMA kernel (bf16, > 128 rows per launch)
-            return (self.fuse_bn_backward and self.dtype == torch.bfloat16 and
-                    g.B * g.Hi * g.Wi // (g.sh * g.sw) > 128 and g.Ci % 8 == 0)
-
-        def bnb_of(blk, C):
-            """fused-sum request for the gradient flowing into `blk`'s output"""
-            req = [(blk["cb"], blk["bn_b"][2], blk["bn_b"][3])]
-            if blk["gd"] is not None:
-                req.append((blk["cd"], blk["bn_d"][2], blk["bn_d"][3]))
-            return req
-
-        # gradient into the last block's output comes from the token kernel: unfused reduce for that one
-        gm, parts = None, None
-        dout = dfeat
-        for bi in range(len(blocks) - 1, -1, -1):
-            blk = blocks[bi]
-            p = blk["p"]
-            C = blk["cb"].shape[-1]
-            if bi == len(blocks) - 3 and after_layer3 is not None:   # both layer-3 blocks (78 % of the stem's weights) are done
+        hook_at = max(i for i, blk in enumerate(blocks) if not blk.p.startswith("patch_embed.layer3."))
+        grad = StemGrad(dfeat)      # from the token kernel: a raw gradient
+        for i in reversed(range(len(blocks))):
+            if i == hook_at and after_layer3 is not None:     # layer 3 (78 % of the stem's weights) is done: its DP bucket can go
                 self._flush_unpacks()
                 after_layer3(self._wgrad_stream())
-            if parts is None:   # dout is an unmasked gradient: classic path (mask + sums in one reduction pass)
-                dcb, gm = self.bn_backward(dout, blk["out"], blk["cb"], p + ".bn2", P, G, blk["bn_b"][2], blk["bn_b"][3],
-                                           want_g=True)
-                parts_d = None
-            else:               # dout is already g = dOut * (out > 0) and the sums exist
-                gm = dout
-                parts_d = parts[1] if len(parts) > 1 else None
-            # downsample gradient as one more tap of the strided conv's class-(0,0) dgrad (HtrvtGemmDesc.A2) instead of its own
-            # parity-class launches plus a residual round trip of the whole input gradient: d(conv1 out) and d(downsample
-            # out) then live back to back in one allocation (the second gather source sits at a fixed offset from the first)
-            fuse_ds = (not self.split and blk["gd"] is not None and self._dgrad_by_class(blk["g1"]) and
-                       2 * blk["ca"].numel() * blk["ca"].element_size() < 2 ** 31 - 64)     # A2 lies behind A inside ONE 2 GiB descriptor
-            pair = self._empty(2, *blk["ca"].shape) if fuse_ds else None
-            dca_out = pair[0] if fuse_ds else None
-            dcd = None
-            if parts is not None:
-                if parts_d is not None and self.merge_bn_backward:
-                    # bn2 and the downsample BN take the same gradient: one pass, gm read once (csrc/bwd.hip bn_bwd_apply2)
-                    co_b = self.bn_backward_coef(parts[0][0], parts[0][1], blk["cb"], p + ".bn2", P, G, blk["bn_b"][2], blk["bn_b"][3])
-                    co_d = self.bn_backward_coef(parts_d[0], parts_d[1], blk["cd"], p + ".downsample.1", P, G, blk["bn_d"][2], blk["bn_d"][3])
-                    dcb = torch.empty_like(blk["cb"])
-                    dcd = pair[1] if fuse_ds else torch.empty_like(blk["cd"])
-                    check(lib.htrvt_bn_bwd_apply2(ptr(gm), ptr(blk["cb"]), ptr(co_b), ptr(dcb), ptr(blk["cd"]), ptr(co_d), ptr(dcd),
-                                                  dcb.numel() // C, C, self.dti, stream()), "bn_bwd_apply2")
-                else:
-                    dcb, _ = self.bn_backward_finish(parts[0][0], parts[0][1], gm, None, blk["cb"], p + ".bn2", P, G,
-                                                     blk["bn_b"][2], blk["bn_b"][3])
-            _, wd2 = self._conv_w(p + ".conv2", P[p + ".conv2.weight"])
-            self.conv_wgrad(dcb, blk["a1"], blk["g2"], G[p + ".conv2.weight"])
-            if can_fuse(blk["g2"]):
-                rows1 = self.dgrad_tiles(blk["g2"])
-                part1 = self._empty(rows1, 2, C, dtype=torch.float32)
-                # a1 = relu(bn1(ca)): the mask is recomputed from ca (read for the sums anyway) instead of reading a1
-                rk = dict(relu_bn=(blk["bn_a"][0], blk["bn_a"][1])) if self.relu_mask_from_bn else dict(relu_src=blk["a1"])
-                g1 = self.conv_dgrad(dcb, wd2, blk["g2"], bnb=[(blk["ca"], blk["bn_a"][2], blk["bn_a"][3], part1)], **rk)
-                dca, _ = self.bn_backward_finish(part1, rows1, g1, None, blk["ca"], p + ".bn1", P, G, blk["bn_a"][2],
-                                                 blk["bn_a"][3], out=dca_out)
-                del g1
-            else:
-                da1 = self.conv_dgrad(dcb, wd2, blk["g2"])
-                dca, _ = self.bn_backward(da1, blk["a1"], blk["ca"], p + ".bn1", P, G, blk["bn_a"][2], blk["bn_a"][3], out=dca_out)
-                del da1
-            del dcb
-            _, wd1 = self._conv_w(p + ".conv1", P[p + ".conv1.weight"])
-            self.conv_wgrad(dca, blk["x"], blk["g1"], G[p + ".conv1.weight"])
-            # what the gradient of this block's INPUT feeds: the previous block's output (ReLU + bn2 [+ downsample BN])
-            prev = blocks[bi - 1] if bi > 0 else None
-            kw, parts = {}, None
-            if prev is not None and can_fuse(blk["g1"]):
-                Cp = prev["cb"].shape[-1]
-                rows = self.dgrad_tiles(blk["g1"])
-                req = bnb_of(prev, Cp)
-                bufs = [self._empty(rows, 2, Cp, dtype=torch.float32) for _ in req]
-                kw = dict(relu_src=prev["out"], bnb=[(x_, m_, r_, b_) for (x_, m_, r_), b_ in zip(req, bufs)])
-                # the bit-mask form is compiled for (one sum set) and (residual + one or two sets)
-                with_res = not (blk["gd"] is not None and fuse_ds)
-                if prev.get("mask") is not None and (len(req) == 1 or with_res):
-                    kw.update(relu_src=prev["mask"], relu_bits=True)
-                parts = [(b_, rows) for b_ in bufs]
-            if blk["gd"] is not None:
-                dcd_out = pair[1] if fuse_ds else None
-                if dcd is not None:
-                    pass                      # came out of the joint pass with bn2 above
-                elif parts_d is not None:
-                    dcd, _ = self.bn_backward_finish(parts_d[0], parts_d[1], gm, None, blk["cd"], p + ".downsample.1", P, G,
-                                                     blk["bn_d"][2], blk["bn_d"][3], out=dcd_out)
-                else:
-                    dcd, _ = self.bn_backward(gm, None, blk["cd"], p + ".downsample.1", P, G, blk["bn_d"][2], blk["bn_d"][3],
-                                              out=dcd_out)
-                _, wdd = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
-                self.conv_wgrad(dcd, blk["x"], blk["gd"], G[p + ".downsample.0.weight"])
-                if fuse_ds:
-                    wdj = self._conv_w_joint_dgrad(p + ".conv1", P[p + ".conv1.weight"], p + ".downsample.0",
-                                                   P[p + ".downsample.0.weight"])
-                    dout = self.conv_dgrad(dca, wdj, blk["g1"], extra=dcd, **kw)
-                else:
-                    dres = self.conv_dgrad(dcd, wdd, blk["gd"])
-                    dout = self.conv_dgrad(dca, wd1, blk["g1"], residual=dres, **kw)
-            else:
-                dout = self.conv_dgrad(dca, wd1, blk["g1"], residual=gm, **kw)
+            grad = self._res_block_bwd(P, G, blocks[i], blocks[i - 1] if i > 0 else None, grad)
+        self._stem_head_bwd(P, G, sv, grad.g, B)
 
-        img, c1 = sv["img"], sv["c1"]
+    def can_fuse(self, g):
+        """the dgrad of `g` runs on the LDS-DMA kernel (bf16, > 128 rows per launch): its epilogue can mask and take BN sums"""
+        return (self.fuse_bn_backward and self.dtype == torch.bfloat16 and
+                g.B * g.Hi * g.Wi // (g.sh * g.sw) > 128 and g.Ci % 8 == 0)
+
+    def _res_block_bwd(self, P, G, blk, prev, grad):
+        """backward of one residual block from the StemGrad of its output: the StemGrad of `prev`, the block in front of it
+        (None: the stem head).  bf16: the ReLU mask of a block's output and the BatchNorm-backward sums of its bn2 (and
+        downsample BN) come from the epilogue of the dgrad GEMM that creates that gradient; float32 keeps the separate pass."""
+        p, bn_a, bn_b, bn_d = blk.p, blk.bn_a, blk.bn_b, blk.bn_d
+        # downsample gradient as one more tap of the strided conv's class-(0,0) dgrad (HtrvtGemmDesc.A2) instead of its own
+        # parity-class launches plus a residual round trip of the whole input gradient: d(conv1 out) and d(downsample
+        # out) then live back to back in one allocation (the second gather source sits at a fixed offset from the first)
+        fuse_ds = (not self.split and blk.gd is not None and self._dgrad_by_class(blk.g1) and
+                   2 * bn_a.x.numel() * bn_a.x.element_size() < 2 ** 31 - 64)     # A2 lies behind A inside ONE 2 GiB descriptor
+        # --- 1. BatchNorm backward of the block's output: dcb = d(conv2 out), gm = dOut * (out > 0) [, dcd = d(downsample out)]
+        if grad.sums is None:      # raw gradient: mask + sums in one reduction pass, then the apply
+            dcb, gm = self.bn_backward(grad.g, blk.out, bn_b, P, G, want_g=True)
+            sums_b = sums_d = None
+        else:                      # the sums are taken out of the record: their buffers die with this call's references
+            gm, sums_b, sums_d = grad.g, grad.sums.pop(0), (grad.sums.pop(0) if grad.sums else None)
+        pair = self._empty(2, *bn_a.x.shape) if fuse_ds else None     # (behind the unfused reduce's own buffers)
+        dca_out, dcd_out, dcd = (pair[0], pair[1], None) if fuse_ds else (None, None, None)
+        if sums_d is not None and self.merge_bn_backward:
+            # bn2 and the downsample BN take the same gradient: one pass, gm read once (csrc/bwd.hip bn_bwd_apply2)
+            co_b = self.bn_backward_coef(*sums_b, bn_b, P, G)
+            co_d = self.bn_backward_coef(*sums_d, bn_d, P, G)
+            dcb = torch.empty_like(bn_b.x)
+            dcd = dcd_out if fuse_ds else torch.empty_like(bn_d.x)
+            C = bn_b.x.shape[-1]
+            check(lib.htrvt_bn_bwd_apply2(ptr(gm), ptr(bn_b.x), ptr(co_b), ptr(dcb), ptr(bn_d.x), ptr(co_d), ptr(dcd),
+                                          dcb.numel() // C, C, self.dti, stream()), "bn_bwd_apply2")
+        elif sums_b is not None:
+            dcb, _ = self.bn_backward_finish(*sums_b, gm, None, bn_b, P, G)
+        del sums_b
+        # --- 2. conv2: weight gradient, dgrad, bn1 backward: dca = d(conv1 out)
+        dca = self._conv2_bwd(P, G, blk, dcb, dca_out)
+        del dcb
+        # --- 3. conv1 [+ downsample]: weight gradient(s), then the dgrad(s) with what they feed folded into the epilogue
+        _, wd1 = self._conv_w(p + ".conv1", P[p + ".conv1.weight"])
+        self.conv_wgrad(dca, blk.x, blk.g1, G[p + ".conv1.weight"])
+        kw, sums = {}, None      # the gradient of this block's INPUT feeds prev's output: ReLU + bn2 [+ downsample BN]
+        if prev is not None and self.can_fuse(blk.g1):
+            bns = [prev.bn_b] + ([prev.bn_d] if prev.gd is not None else [])
+            bnb, sums = self._bnb_request(bns, self.dgrad_tiles(blk.g1))
+            kw = dict(relu_src=prev.out, bnb=bnb)
+            # the bit-mask form is compiled for (one sum set) and (residual + one or two sets); fuse_ds: no residual
+            if prev.mask is not None and (len(bns) == 1 or not fuse_ds):
+                kw.update(relu_src=prev.mask, relu_bits=True)
+        if blk.gd is None:
+            return StemGrad(self.conv_dgrad(dca, wd1, blk.g1, residual=gm, **kw), sums)
+        if dcd is None and sums_d is not None:      # (else it came out of the joint pass with bn2 above)
+            dcd, _ = self.bn_backward_finish(*sums_d, gm, None, bn_d, P, G, out=dcd_out)
+        elif dcd is None:
+            dcd, _ = self.bn_backward(gm, None, bn_d, P, G, out=dcd_out)
+        _, wdd = self._conv_w(p + ".downsample.0", P[p + ".downsample.0.weight"])
+        self.conv_wgrad(dcd, blk.x, blk.gd, G[p + ".downsample.0.weight"])
+        if fuse_ds:
+            wdj = self._conv_w_joint_dgrad(p + ".conv1", P[p + ".conv1.weight"], p + ".downsample.0", P[p + ".downsample.0.weight"])
+            return StemGrad(self.conv_dgrad(dca, wdj, blk.g1, extra=dcd, **kw), sums)
+        dres = self.conv_dgrad(dcd, wdd, blk.gd)
+        return StemGrad(self.conv_dgrad(dca, wd1, blk.g1, residual=dres, **kw), sums)
+
+    def _conv2_bwd(self, P, G, blk, dcb, out):
+        """conv2's weight gradient and dgrad, then bn1's backward (written into `out` when given): d(conv1 out)"""
+        p, bn_a = blk.p, blk.bn_a
+        _, wd2 = self._conv_w(p + ".conv2", P[p + ".conv2.weight"])
+        self.conv_wgrad(dcb, blk.a1, blk.g2, G[p + ".conv2.weight"])
+        if not self.can_fuse(blk.g2):
+            da1 = self.conv_dgrad(dcb, wd2, blk.g2)
+            return self.bn_backward(da1, blk.a1, bn_a, P, G, out=out)[0]
+        bnb, sums = self._bnb_request([bn_a], self.dgrad_tiles(blk.g2))
+        # a1 = relu(bn1(ca)): the mask is recomputed from ca (read for the sums anyway) instead of reading a1
+        rk = dict(relu_bn=(bn_a.coef.scale, bn_a.coef.shift)) if self.relu_mask_from_bn else dict(relu_src=blk.a1)
+        g1 = self.conv_dgrad(dcb, wd2, blk.g2, bnb=bnb, **rk)
+        return self.bn_backward_finish(*sums[0], g1, None, bn_a, P, G, out=out)[0]
+
+    def _stem_head_bwd(self, P, G, sv, dout, B):
+        """the first max-pool + bn1 + conv1 (Cin = 1) from the gradient of the pooled activations"""
+        st = stream()
+        img, c1, bn = sv["img"], sv["c1"], sv["bn1"]
         u8 = 1 if img.dtype == torch.uint8 else 0
-        sc, sf, mean, rstd = sv["bn1"]
         _, Hh, W, C1 = sv["c1_shape"]
         if self.fuse_conv1_backward and self._bn_train:
-            # Cin = 1: dW1, dgamma, dbeta from per-channel sums over the pooled gradient (csrc/conv1_bwd.hip)
+            # dW1, dgamma, dbeta from per-channel sums over the pooled gradient (csrc/conv1_bwd.hip)
             partial = self._empty(lib.htrvt_conv1_bwd_rows(B, 2 * Hh), lib.htrvt_conv1_bwd_row_floats(C1), dtype=torch.float32)
             check(lib.htrvt_conv1_bwd(ptr(img), ptr(sv["stats"]), ptr(dout), ptr(sv["idx"]), ptr(P["patch_embed.conv1.weight"]),
-                                      ptr(P["patch_embed.bn1.weight"]), ptr(mean), ptr(rstd), ptr(partial),
+                                      ptr(P["patch_embed.bn1.weight"]), ptr(bn.mean), ptr(bn.rstd), ptr(partial),
                                       ptr(G["patch_embed.conv1.weight"]), ptr(G["patch_embed.bn1.weight"]),
                                       ptr(G["patch_embed.bn1.bias"]), B, 2 * Hh, W, C1, self.dti, u8, st), "conv1_bwd")
-        else:
-            g = torch.empty_like(c1)
-            check(lib.htrvt_maxpool_bwd(ptr(dout), ptr(sv["idx"]), ptr(c1), ptr(sc), ptr(sf), ptr(g), B, Hh, W, C1, self.dti, st),
-                  "maxpool_bwd")
-            dc1, _ = self.bn_backward(g, None, c1, "patch_embed.bn1", P, G, mean, rstd)
-            del g
-            nblk = lib.htrvt_conv1_wgrad_blocks(B, 2 * Hh)
-            partial = self._empty(nblk, C1 * 9, dtype=torch.float32)
-            check(lib.htrvt_conv1_wgrad(ptr(img), ptr(sv["stats"]), ptr(dc1), ptr(G["patch_embed.conv1.weight"]), ptr(partial),
-                                        B, 2 * Hh, W, C1, self.dti, u8, st), "conv1_wgrad")
+            return
+        g = torch.empty_like(c1)
+        check(lib.htrvt_maxpool_bwd(ptr(dout), ptr(sv["idx"]), ptr(c1), ptr(bn.scale), ptr(bn.shift), ptr(g), B, Hh, W, C1,
+                                    self.dti, st), "maxpool_bwd")
+        dc1, _ = self.bn_backward(g, None, SavedBN(bn, "patch_embed.bn1", c1), P, G)
+        del g
+        partial = self._empty(lib.htrvt_conv1_wgrad_blocks(B, 2 * Hh), C1 * 9, dtype=torch.float32)
+        check(lib.htrvt_conv1_wgrad(ptr(img), ptr(sv["stats"]), ptr(dc1), ptr(G["patch_embed.conv1.weight"]), ptr(partial),
+                                    B, 2 * Hh, W, C1, self.dti, u8, st), "conv1_wgrad")

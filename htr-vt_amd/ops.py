@@ -61,6 +61,15 @@ class ConvGeom:
         d.nB, d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.Co = self.B, self.Hi, self.Wi, self.Ci, self.Ho, self.Wo, self.Co
         d.kh, d.kw, d.sh, d.sw, d.ph, d.pw = self.kh, self.kw, self.sh, self.sw, self.ph, self.pw
 
+    def parity_classes(self):
+        """(a, b, taps reaching the class, Hq, Wq) per input-pixel parity class (a, b) of the dgrad, row-major: the class's
+        Hq x Wq pixels per image are those at (a + sh i, b + sw j); a stride-1 conv has the one class (0, 0)"""
+        for a in range(self.sh):
+            for b in range(self.sw):
+                nt = sum(1 for dy in range(self.kh) if (a + self.ph - dy) % self.sh == 0) * \
+                     sum(1 for dx in range(self.kw) if (b + self.pw - dx) % self.sw == 0)
+                yield a, b, nt, (self.Hi - a + self.sh - 1) // self.sh, (self.Wi - b + self.sw - 1) // self.sw
+
 
 def gemm(A, B, Cout, *, dtype, M, N, K, lda, ldb, ldc, a_layout=KMAJOR, b_layout=KMAJOR, gather=0, geom=None,
          Cpad=0, batch=1, batch_inner=1, sA=(0, 0), sB=(0, 0), sC=(0, 0), split_k=1, alpha=1.0, act=0, c_f32=False,

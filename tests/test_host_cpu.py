@@ -106,6 +106,43 @@ def test_create_model_matches_reference_init(golden_dir):
         HTR_VT.create_model(80, [64, 512], embed_dim=256)
 
 
+def test_stem_block_table_matches_the_model():
+    """ModelShape.stem_blocks() / stem_convs() against the modules of the v1 model at (64, 512)"""
+    from htrvt_amd.model import HTR_VT
+    m = HTR_VT.create_model(nb_cls=80, img_size=[64, 512])
+    mods = dict(m.named_modules())
+    convs = [(n, mod) for n, mod in mods.items() if isinstance(mod, torch.nn.Conv2d) and n.startswith("patch_embed.layer")]
+    table = m._shape.stem_convs()
+    assert [t[0] for t in table] == [n for n, _ in convs]
+    for (name, Ci, Co, k, stride, pad), (_, mod) in zip(table, convs):
+        assert (Ci, Co, k, stride, pad) == (mod.in_channels, mod.out_channels, mod.kernel_size[0], mod.stride, mod.padding[0]), name
+    blocks = m._shape.stem_blocks()
+    assert len(blocks) == 6
+    for b in blocks:
+        assert b.downsample == (getattr(mods[b.prefix], "downsample", None) is not None), b.prefix
+        assert (b.Cin, b.planes, b.stride) == (mods[b.prefix].conv1.in_channels, mods[b.prefix].conv1.out_channels, mods[b.prefix].conv1.stride)
+    stem = [n for n, mod in mods.items() if isinstance(mod, torch.nn.Conv2d) and n.startswith("patch_embed.") and n != "patch_embed.conv1"]
+    assert sorted(t[0] for t in table) == sorted(stem) and len(set(stem)) == len(stem) == 15
+
+
+@pytest.mark.parametrize("Hi,Wi", [(5, 7), (4, 8)])
+@pytest.mark.parametrize("k,stride,pad", [(3, (2, 2), 1), (3, (2, 1), 1), (3, (1, 1), 1), (1, (2, 2), 0)])
+def test_conv_geom_parity_classes(k, stride, pad, Hi, Wi):
+    import htrvt_amd  # noqa: F401
+    from htrvt_amd.ops import ConvGeom
+    g = ConvGeom(2, Hi, Wi, 8, 16, k, stride, pad)
+    classes = list(g.parity_classes())
+    assert [(a, b) for a, b, _, _, _ in classes] == [(a, b) for a in range(stride[0]) for b in range(stride[1])]
+    assert sum(Hq * Wq for _, _, _, Hq, Wq in classes) == Hi * Wi
+    assert sum(nt for _, _, nt, _, _ in classes) == k * k
+    for a, b, nt, Hq, Wq in classes:
+        assert nt == sum(1 for dy in range(k) for dx in range(k)
+                         if (a + pad - dy) % stride[0] == 0 and (b + pad - dx) % stride[1] == 0)
+        assert (Hq, Wq) == (len(range(a, Hi, stride[0])), len(range(b, Wi, stride[1])))
+    if k == 1:
+        assert [(a, b) for a, b, nt, _, _ in classes if nt] == [(0, 0)]
+
+
 def test_no_cpu_fallback():
     from htrvt_amd.model import HTR_VT
     m = HTR_VT.create_model(nb_cls=80, img_size=[64, 512])

@@ -46,7 +46,7 @@ def gpu_ladder(cfg, sd, x, keep, train, fold_eval=False):
         st = [("conv1+bn+relu+pool", sv["stem_blocks"][0]["x"])]
         for blk in sv["stem_blocks"]:
             p = blk["p"].replace("patch_embed.", "")
-            st += [(p + " conv1 (raw)", blk["ca"]), (p + " relu(bn1)", blk["a1"]), (p + " conv2 (raw)", blk["cb"]), (p + " out", blk["out"])]
+            st += [(p + " conv1 (raw)", blk.bn_a.x), (p + " relu(bn1)", blk["a1"]), (p + " conv2 (raw)", blk.bn_b.x), (p + " out", blk["out"])]
         for e in sv["enc"]:
             st += [(e["p"] + " input", e["x0"]), (e["p"] + " attn out (O)", e["O"]), (e["p"] + " after attn", e["x1"]),
                    (e["p"] + " gelu(fc1)", e["h"])]
