@@ -153,8 +153,7 @@ __device__ __forceinline__ void gemm_hwgrad_body(const P& p, const int block_x) 
   DmaLoader<BN, HTRVT_MNMAJOR, 0, H::NWY> ly;        // dY: plain MN-major rows (k = pixel)
   const bool yload = wave < H::NWY;                  // wave-uniform
   ly.init(p, p.B, p.ldb, n0, p.N, yload ? wave : 0, lane);
-  const unsigned long long xa = (unsigned long long)p.A;
-  const i32x4_t rsrcX = i32x4_t{(int)(unsigned)(xa & 0xffffffffull), (int)(unsigned)((xa >> 32) & 0xffffull), (int)OOB, 0x00020000};
+  const i32x4_t rsrcX = make_rsrc(p.A);
   const int npx = (wave < H::XPIECES - NW * (H::NPX_MAX - 1)) ? H::NPX_MAX : H::NPX_MAX - 1;   // wave-uniform
   const int per_tile = npx + (wave < H::NWY ? H::NPY : 0);      // DMA pieces this wave issues per k-tile
   auto wait_one_tile_in_flight = [&]() {   // everything but this wave's newest k-tile has landed (the count is an immediate)
@@ -401,9 +400,7 @@ __device__ __forceinline__ void gemm_hwgrad16_body(const P& p, const int block_x
   const int crow = (wm & 1) * (CC / 2);
 
   // ---- DMA bookkeeping: per piece (row / k-row, source chunk) of this lane, formed once ----
-  const unsigned long long xa = (unsigned long long)p.A, ya = (unsigned long long)p.B;
-  const i32x4_t rsrcX = i32x4_t{(int)(unsigned)(xa & 0xffffffffull), (int)(unsigned)((xa >> 32) & 0xffffull), (int)OOB, 0x00020000};
-  const i32x4_t rsrcY = i32x4_t{(int)(unsigned)(ya & 0xffffffffull), (int)(unsigned)((ya >> 32) & 0xffffull), (int)OOB, 0x00020000};
+  const i32x4_t rsrcX = make_rsrc(p.A), rsrcY = make_rsrc(p.B);
   int xr[H::NPX], xc[H::NPX];      // xr: source pixel of this lane's LDS row, relative to the k-tile's first (SW = 1: w0 - 1; SW = 2: 2 w0)
   bool xok[H::NPX];
 #pragma unroll
