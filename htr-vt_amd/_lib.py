@@ -141,7 +141,7 @@ PROTOTYPES = {
     "htrvt_attn_relpos_dropout_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, f32,
                                             i32, vp]),
     "htrvt_residual_dropout": (i32, [vp, vp, vp, i32, i64, i32, vp, f32, f32, i32, vp]),
-    "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "htrvt_sgm_xent_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "htrvt_sgm_convert": (i32, [vp, i32, vp, i32, i64, i32, vp]),
     "htrvt_attn_local_supported": (i32, [i32, i32, i32]),

@@ -146,17 +146,25 @@ __global__ __launch_bounds__(NT) void sgm_dropout_kernel(const T* __restrict__ x
 }
 
 // ------------------------------------------------------------------ cross-entropy
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // logits float32 [rows][ldv], row r = (b, dir, l); one wave per row
 __global__ __launch_bounds__(NT) void sgm_xent_fwd_kernel(const float* __restrict__ logits, int ldv, int V, long long rows,
                                                           int L, const long long* __restrict__ tgt, const float* __restrict__ mask,
                                                           float* __restrict__ out_l, float* __restrict__ out_r,
-                                                          float* __restrict__ lse, float* __restrict__ rowloss) {
+                                                          float* __restrict__ lse, float* __restrict__ rowloss,
+                                                          double* __restrict__ rowloss64) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const int b = (int)(r / (2 * L)), rem = (int)(r % (2 * L)), dir = rem / L, l = rem % L;
   const float* x = logits + r * ldv;
-  float* o = (dir ? out_r : out_l) + ((long long)b * L + l) * V;
+  float* o = dir ? out_r : out_l;        // NULL: no copy of this direction
+  if (o) o += ((long long)b * L + l) * V;
   float m = -INFINITY;
   for (int c = lane; c < V; c += 64) {
     const float v = x[c];
@@ -168,27 +176,36 @@ __global__ __launch_bounds__(NT) void sgm_xent_fwd_kernel(const float* __restric
   for (int c = lane; c < V; c += 64) s += __expf(x[c] - m);
   s = wave_sum(s);
   const float ls = m + __logf(s);
+  // the same row loss in float64 for the reduction: the scalar loss is then the true masked mean rounded once, whatever
+  // the float32 row losses above round to
+  double sd = 0.0;
+  for (int c = lane; c < V; c += 64) sd += exp((double)x[c] - (double)m);
+  sd = wave_sum_f64(sd);
   if (lane == 0) {
     const long long bl = (long long)b * L + l;
     const int t = clamp_id(tgt[bl], V);
     lse[r] = ls;
     rowloss[r] = (ls - x[t]) * mask[bl];
+    rowloss64[r] = ((double)m + log(sd) - (double)x[t]) * (double)mask[bl];
   }
 }
 
-// loss = sum(rowloss) / den, den = 2 max(sum(mask), 1).  One block, fixed order.
-__global__ __launch_bounds__(NT) void sgm_xent_reduce_kernel(const float* __restrict__ rowloss, long long rows,
+// loss = sum(rowloss64) / den in float64, rounded once; den = 2 max(sum(mask), 1).  One block, fixed order.
+__global__ __launch_bounds__(NT) void sgm_xent_reduce_kernel(const double* __restrict__ rowloss64, long long rows,
                                                              const float* __restrict__ mask, long long nmask,
                                                              float* __restrict__ loss, float* __restrict__ den) {
   __shared__ float red[8];
-  float s = 0.f, m = 0.f;
-  for (long long i = threadIdx.x; i < rows; i += NT) s += rowloss[i];
+  __shared__ double red64[4];
+  double s = 0.0;
+  float m = 0.f;
+  for (long long i = threadIdx.x; i < rows; i += NT) s += rowloss64[i];
   for (long long i = threadIdx.x; i < nmask; i += NT) m += mask[i];
-  s = block_sum_256(s, red);
-  m = block_sum_256(m, red);
+  s = wave_sum_f64(s);
+  if ((threadIdx.x & 63) == 0) red64[threadIdx.x >> 6] = s;
+  m = block_sum_256(m, red);               // its barriers also publish red64
   if (threadIdx.x == 0) {
     const float d = 2.0f * fmaxf(m, 1.0f);
-    loss[0] = s / d;
+    loss[0] = (float)((red64[0] + red64[1] + red64[2] + red64[3]) / (double)d);
     den[0] = d;
   }
 }
@@ -309,16 +326,17 @@ extern "C" int htrvt_sgm_dropout(const void* x, void* y, int64_t n, const int64_
 }
 
 extern "C" int htrvt_sgm_xent_fwd(const float* logits, int ldv, int V, int B, int L, const int64_t* tgt, const float* mask,
-                                  float* logits_l, float* logits_r, float* lse, float* rowloss, float* loss, float* den,
-                                  void* stream) {
+                                  float* logits_l, float* logits_r, float* lse, float* rowloss, double* rowloss64,
+                                  float* loss, float* den, void* stream) {
   HTRVT_REQUIRE(V >= 1 && ldv >= V && B >= 0 && L >= 0, "htrvt_sgm_xent_fwd: bad sizes");
   HTRVT_REQUIRE(loss && den, "htrvt_sgm_xent_fwd: null loss / denominator");
   const long long rows = 2ll * B * L;
+  HTRVT_REQUIRE(rows == 0 || (logits && tgt && mask && lse && rowloss && rowloss64), "htrvt_sgm_xent_fwd: null buffer");
   hipStream_t st = (hipStream_t)stream;
   if (rows > 0)
     hipLaunchKernelGGL(sgm_xent_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(NT), 0, st, logits, ldv, V, rows, L,
-                       (const long long*)tgt, mask, logits_l, logits_r, lse, rowloss);
-  hipLaunchKernelGGL(sgm_xent_reduce_kernel, dim3(1), dim3(NT), 0, st, rowloss, rows, mask, rows / 2, loss, den);
+                       (const long long*)tgt, mask, logits_l, logits_r, lse, rowloss, rowloss64);
+  hipLaunchKernelGGL(sgm_xent_reduce_kernel, dim3(1), dim3(NT), 0, st, rowloss64, rows, mask, rows / 2, loss, den);
   return check_launch("sgm_xent_fwd");
 }
 

@@ -102,9 +102,10 @@ class _SGMFunction(torch.autograd.Function):
         logits_l, logits_r = _empty((B, L, V), f32, dev), _empty((B, L, V), f32, dev)
         loss, den = _empty((), f32, dev), _empty(1, f32, dev)
         lse, rowloss = _empty(max(R, 1), f32, dev), _empty(max(R, 1), f32, dev)
+        rowloss64 = _empty(max(R, 1), torch.float64, dev)      # scratch: the scalar loss is reduced in float64
         st = stream()
         if R == 0:           # no character in the batch: loss 0, zero gradients
-            check(lib.htrvt_sgm_xent_fwd(None, Vp, V, B, L, None, None, None, None, None, None, ptr(loss), ptr(den), st),
+            check(lib.htrvt_sgm_xent_fwd(None, Vp, V, B, L, None, None, None, None, None, None, None, ptr(loss), ptr(den), st),
                   "sgm_xent_fwd")
             ctx.empty = True
             ctx.shapes = [t.shape for t in params] + [vis.shape]
@@ -143,7 +144,7 @@ class _SGMFunction(torch.autograd.Function):
         logits = _empty((R, Vp), f32, dev)
         gemm(Od, wc, logits, dtype=cdt, M=R, N=Vp, K=D, lda=D, ldb=D, ldc=Vp, bias=bc, c_f32=True)
         check(lib.htrvt_sgm_xent_fwd(ptr(logits), Vp, V, B, L, ptr(tgt), ptr(mask), ptr(logits_l), ptr(logits_r), ptr(lse),
-                                     ptr(rowloss), ptr(loss), ptr(den), st), "sgm_xent_fwd")
+                                     ptr(rowloss), ptr(rowloss64), ptr(loss), ptr(den), st), "sgm_xent_fwd")
         if need:
             ctx.save_for_backward(left, right, tgt, mask, A, Qp, qm, qr, Q, visc, km, kr, K, Pm, Od, logits, lse, den, wt, wc,
                                   seed, P["q_norm.weight"], P["kv_norm.weight"])

@@ -486,7 +486,8 @@ int htrvt_line_prepare(const uint8_t* src, const HtrvtLineImage* table, uint8_t*
  *   device int64.  The backward is the same call on the gradient.  n a multiple of 4 (float32) / 8 (bfloat16).
  * htrvt_sgm_xent_fwd: logits float32 [2 B L][ldv]: row log-softmax over the first V columns, NLL at tgt (clamped) times
  *   mask; logits_l / logits_r (may be NULL) float32 [B][L][V] copies; lse, rowloss [2 B L] scratch kept for the backward;
- *   den[0] = 2 max(sum mask, 1), loss[0] = sum / den[0], both by a fixed-shape ordered reduction.
+ *   rowloss64 [2 B L] float64 scratch: the row losses again, from which the scalar is reduced;
+ *   den[0] = 2 max(sum mask, 1), loss[0] = sum / den[0] rounded once from float64, both by a fixed-shape ordered reduction.
  * htrvt_sgm_xent_bwd: dlogits [2 B L][ldv] (dtype) = (softmax - onehot) * mask * g[0] / den[0] (+ dlogits_l / _r, may be
  *   NULL; g may be NULL = 0), zero in the columns V .. ldv-1.
  * htrvt_sgm_convert: dst = src (accumulate: dst += src), element types src_dtype / dst_dtype. */
@@ -499,7 +500,8 @@ int htrvt_sgm_query_bwd(const int64_t* left, const int64_t* right, const void* d
                         float* ddir_left, float* ddir_right, int B, int L, int S, int V, int d_txt, int dtype, void* stream);
 int htrvt_sgm_dropout(const void* x, void* y, int64_t n, const int64_t* seed, float p, int dtype, void* stream);
 int htrvt_sgm_xent_fwd(const float* logits, int ldv, int V, int B, int L, const int64_t* tgt, const float* mask,
-                       float* logits_l, float* logits_r, float* lse, float* rowloss, float* loss, float* den, void* stream);
+                       float* logits_l, float* logits_r, float* lse, float* rowloss, double* rowloss64, float* loss, float* den,
+                       void* stream);
 int htrvt_sgm_xent_bwd(const float* logits, int ldv, int V, int B, int L, const int64_t* tgt, const float* mask,
                        const float* lse, const float* den, const float* g, const float* dlogits_l, const float* dlogits_r,
                        void* dlogits, int dtype, void* stream);

@@ -1,6 +1,8 @@
 """The SGM drop-in on the MI355X: the context batch, the head (float32 / bfloat16) and model_sgm_2's encoder with the
-feature tap against the reference run in float64 on the CPU (tests/golden/sgm.npz, tools/make_goldens_sgm.py); padding,
+feature tap against the reference run in float64 on the CPU (tests/golden/sgm.npz, tools/make_goldens_sgm.py), and the head at 600 query rows
+(three chunks of the query backward) against tests/sgm_refs.py in float64; padding,
 the dropout generator, bitwise reproducibility and SAM-style `p.data` rebinding."""
+import functools
 import os
 from functools import partial
 
@@ -9,6 +11,7 @@ import pytest
 import torch
 
 import sgm_cases as C
+import sgm_refs as R
 from htrvt_amd._lib import lib
 from htrvt_amd.ops import ptr, stream
 
@@ -93,6 +96,67 @@ def test_sgm_head_against_reference(golden_dir, dtype, case):
             assert rn < (2e-4 if f32 else 4e-2), (n, rn)
         print(f"{case} {dtype} grad {n}: rel-to-max {e:.3e} cosine {cos:.7f}")
         assert e < (2e-4 if f32 else 4e-2) and cos > (0.99999 if f32 else 0.999), (n, e, cos)
+
+
+MULTI_CHUNK = (6, 50, 32, 64, 40, 30, 5)      # (B, L, N, D, d_txt, V, S): R = 2 B L = 600 rows, three chunks of the query backward
+
+
+@functools.lru_cache(maxsize=None)
+def _multi_chunk_reference():
+    """tests/sgm_refs.head in float64 under autograd, once for both dtypes: (ctx, vis, head seed, loss, logits, gradients)"""
+    B, L, N, D, dtx, V, S = MULTI_CHUNK
+    stoi = C.vocab_for(V)
+    ids = [[stoi[ch] for ch in t] for t in C.random_texts(B, L, V, seed=61)]
+    ctx = R.context_batch(ids, S, stoi["<pad>"], stoi["<bos_left>"], stoi["<eos>"])
+    vis = C.vis_tokens(B, N, D, seed=N + D + 1)
+    h = _new_head(MULTI_CHUNK, torch.float32, 161)
+    params = {n: p.detach().double().requires_grad_(True) for n, p in h.named_parameters()}
+    v = vis.double().requires_grad_(True)
+    loss, ll, lr = R.head(params, v, *ctx)
+    loss.backward()
+    grads = {n: p.grad.numpy() for n, p in params.items()}
+    grads["vis"] = v.grad.numpy()
+    return ctx, vis, loss.item(), {"logits_l": ll.detach().numpy(), "logits_r": lr.detach().numpy()}, grads
+
+
+def _new_head(shape, dtype, seed):
+    from htrvt_amd.sgm.model.sgm_head import SGMHead
+    B, L, N, D, dtx, V, S = shape
+    torch.manual_seed(seed)
+    h = SGMHead(D, V, d_txt=dtx, sub_str_len=S, compute_dtype=dtype)
+    C.perturb_head(h, seed)
+    return h
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_sgm_head_multi_chunk_against_float64(dtype):
+    """the head where the query backward sums three chunks (the golden cases stay inside one), the gates of
+    test_sgm_head_against_reference"""
+    from htrvt_amd.sgm.model.sgm_head import make_context_batch
+    B, L, N, D, dtx, V, S = MULTI_CHUNK
+    ctx, vis, loss_ref, logits_ref, grads_ref = _multi_chunk_reference()
+    assert ctx[0].shape == (B, L, S) and 2 * B * L == 600
+    dev_ctx = make_context_batch(C.random_texts(B, L, V, seed=61), C.vocab_for(V), S)
+    assert all(torch.equal(a.cpu(), b) for a, b in zip(dev_ctx, ctx))
+    h = _new_head(MULTI_CHUNK, dtype, 161).cuda().eval()
+    out, grads = _run(h, vis.cuda(), dev_ctx)
+    f32 = dtype == torch.float32
+    loss = float(out["loss_sgm"])
+    print(f"multi-chunk {dtype} loss {loss:.7f} float64 {loss_ref:.7f}")
+    assert abs(loss - loss_ref) <= (1e-5 if f32 else 1e-2) * abs(loss_ref), loss
+    for n in ("logits_l", "logits_r"):
+        e, cos = _cmp(out[n].detach().cpu().numpy(), logits_ref[n])
+        print(f"multi-chunk {dtype} {n}: rel-to-max {e:.3e} cosine {cos:.7f}")
+        assert e < (3e-5 if f32 else 3e-2) and cos > (0.99999 if f32 else 0.999), (n, e, cos)
+    assert set(grads) == set(grads_ref)
+    for n, t in grads.items():
+        e, cos = _cmp(t.cpu().numpy(), grads_ref[n])
+        print(f"multi-chunk {dtype} grad {n}: rel-to-max {e:.3e} cosine {cos:.7f}")
+        assert e < (2e-4 if f32 else 4e-2) and cos > (0.99999 if f32 else 0.999), (n, e, cos)
+    out2, grads2 = _run(h, vis.cuda(), dev_ctx)
+    assert torch.equal(out["loss_sgm"], out2["loss_sgm"])
+    for n in grads:
+        assert torch.equal(grads[n], grads2[n]), n
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
