@@ -183,24 +183,51 @@ __global__ __launch_bounds__(NT) void conv1_fwd_kernel(const void* __restrict__ 
 // that htrvt_bn_finalize takes.  conv1_bwd.hip uses the same identities for the backward.
 constexpr int NMOM = 54;   // 9 tap sums + 45 upper-triangle tap products
 
-// one block per MOM_R consecutive conv rows of one image: partial[block][64] (54 used); the 54 block reductions are
-// amortised over MOM_R rows
+// one block per MOM_R consecutive conv rows of one image: partial[block][64]; the block reductions are amortised over
+// MOM_R rows.  The 45 products are summed in float32 over the float32-whitened image, as the convolution sees it.  The 9
+// tap sums X are sums of a zero-mean image: |X[t]| is a thousandth of sum |x_t|, and float32 whitening alone (equal pixels
+// round the same way) moves it by more than a float32 ulp of sum |x_t|.  They are formed in double from the pixels as they
+// are loaded -- per tap row r the total of its image rows, of their first and of their last column: X[3r] = total - last,
+// X[3r+1] = total, X[3r+2] = total - first -- and leave as float32 hi + lo pairs: columns 0..8 hi, 54..62 lo.
 constexpr int MOM_R = 4;
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __global__ __launch_bounds__(NT) void stem_moments_kernel(const void* __restrict__ img, const float* __restrict__ stats,
                                                           float* __restrict__ partial, int H, int W, int u8) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* rows = reinterpret_cast<float*>(smem_raw);  // [2 MOM_R + 1][W+2]
   __shared__ float red[NT / 64][NMOM];
+  __shared__ double xred[NT / 64][9];
   const int Ho = H / 2, groups = (Ho + MOM_R - 1) / MOM_R;
   const int b = blockIdx.x / groups, ho0 = (blockIdx.x - b * groups) * MOM_R;
   const int nr = min(MOM_R, Ho - ho0);
   const float mean = stats[2 * b], rstd = stats[2 * b + 1];
   const int WP = W + 2;
+  double xs[9];   // [3 r + k]: k = 0 total, 1 first column, 2 last column of the image rows under tap row r
+#pragma unroll
+  for (int k = 0; k < 9; ++k) xs[k] = 0.0;
   for (int i = threadIdx.x; i < (2 * nr + 1) * WP; i += NT) {
     const int r = i / WP, c = i - r * WP;
     const int hi = 2 * ho0 - 1 + r, wi = c - 1;
     float v = 0.f;
-    if (hi >= 0 && hi < H && wi >= 0 && wi < W) v = (load_pixel(img, ((long long)b * H + hi) * W + wi, u8) - mean) * rstd;
+    if (hi >= 0 && hi < H && wi >= 0 && wi < W) {
+      const long long at = ((long long)b * H + hi) * W + wi;
+      const float p = load_pixel(img, at, u8);   // uint8: the float32 value / 255, so that a uint8 image equals its float conversion
+      v = (p - mean) * rstd;
+      const double d = ((double)p - (double)mean) * (double)rstd;
+      // staged row r is tap row 0 of conv row r / 2 and tap row 2 of conv row r / 2 - 1 (r even), tap row 1 of (r - 1) / 2 (r odd)
+      const bool m[3] = {(r & 1) == 0 && (r >> 1) < nr, (r & 1) == 1, (r & 1) == 0 && r >= 2};
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const double dq = m[q] ? d : 0.0;
+        xs[3 * q] += dq;
+        xs[3 * q + 1] += wi == 0 ? dq : 0.0;
+        xs[3 * q + 2] += wi == W - 1 ? dq : 0.0;
+      }
+    }
     rows[i] = v;
   }
   __syncthreads();
@@ -216,29 +243,42 @@ __global__ __launch_bounds__(NT) void stem_moments_kernel(const void* __restrict
       for (int c = 0; c < 3; ++c) x[r * 3 + c] = rows[(2 * q + r) * WP + px + c];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      acc[t] += x[t];
 #pragma unroll
       for (int u = t; u < 9; ++u) acc[9 + t * 9 - t * (t - 1) / 2 + (u - t)] += x[t] * x[u];   // upper triangle, row-major
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < NMOM; ++k) {
+  for (int k = 9; k < NMOM; ++k) {
     const float v = wave_sum(acc[k]);
     if (lane == 0) red[wave][k] = v;
   }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const double v = wave_sum_f64(xs[k]);
+    if (lane == 0) xred[wave][k] = v;
+  }
   __syncthreads();
   if (threadIdx.x < 64) {
+    const int k = threadIdx.x;
     float v = 0.f;
-    if (threadIdx.x < NMOM) {
+    if (k >= 9 && k < NMOM) {
 #pragma unroll
-      for (int w = 0; w < NT / 64; ++w) v += red[w][threadIdx.x];
+      for (int w = 0; w < NT / 64; ++w) v += red[w][k];
+    } else if (k < 9 || k < NMOM + 9) {
+      const int t = k < 9 ? k : k - NMOM, r = t / 3, cc = t - 3 * r;
+      double X = 0.0;
+#pragma unroll
+      for (int w = 0; w < NT / 64; ++w) X += xred[w][3 * r] - (cc == 0 ? xred[w][3 * r + 2] : cc == 2 ? xred[w][3 * r + 1] : 0.0);
+      const float hi = (float)X;
+      v = k < 9 ? hi : (float)(X - (double)hi);
     }
-    partial[(long long)blockIdx.x * 64 + threadIdx.x] = v;
+    partial[(long long)blockIdx.x * 64 + k] = v;
   }
 }
 
-// one block of 512 threads: 64 columns x 8 row lanes sum the partial rows in double, then thread c < C forms the
+// one block of 512 threads: 64 columns x 8 row lanes sum the partial rows in double (X[t] = column t + column 54 + t, the
+// hi and lo parts), then thread c < C forms the
 // channel's (sum y, sum y^2) -> colstats[0][c], colstats[1][c]
 constexpr int SS_RL = 8;
 __global__ __launch_bounds__(64 * SS_RL) void stem_stats_kernel(const float* __restrict__ partial, int nrows,
@@ -263,6 +303,8 @@ __global__ __launch_bounds__(64 * SS_RL) void stem_stats_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < SS_RL; ++k) t += red[k][threadIdx.x];
     if (threadIdx.x < 9) {
+#pragma unroll
+      for (int k = 0; k < SS_RL; ++k) t += red[k][NMOM + threadIdx.x];
       X[threadIdx.x] = t;
     } else {
       int k = threadIdx.x - 9, i = 0;
@@ -822,7 +864,9 @@ extern "C" int htrvt_stem_fwd(const void* img, const float* stats, const float* 
   else
     hipLaunchKernelGGL(stem_fused_fwd_kernel<float>, grid, dim3(NT), smem, (hipStream_t)stream, img, stats, w, scale, shift,
                        (float*)y, idx, H, W, C, nthr, img_u8);
-  return check_launch("stem_fwd");
+  const int rc = check_launch("stem_fwd");
+  if (rc == 0) set_last_kernel(dtype == HTRVT_BF16 ? "stem_fused_fwd_kernel<bf16_t>" : "stem_fused_fwd_kernel<float>");
+  return rc;
 }
 
 extern "C" int htrvt_bn_finalize(const float* partial, int rows, int C, float count, const float* gamma, const float* beta,

@@ -196,7 +196,9 @@ int stem_mfma_try_launch(const void* img, const float* stats, const float* w, co
   hipLaunchKernelGGL(stem_mfma_fwd_kernel, dim3(B * Hp), dim3(SM_NT), smem, st, img, stats, w, scale, shift, (bf16_t*)y, idx, H, W,
                      C, img_u8, nblk, RS);
   const int rc = check_launch("stem_mfma_fwd");
-  return rc ? rc : 1;
+  if (rc) return rc;
+  set_last_kernel("stem_mfma_fwd_kernel");
+  return 1;
 }
 
 }  // namespace htrvt

@@ -42,7 +42,8 @@ int htrvt_version(void);
 const char* htrvt_last_error(void);
 /* symbol of the MFMA kernel the last htrvt_gemm call of this thread launched, spelled as rocprofv3 prints it
  * (e.g. "gemm_dma_kernel<256, 192, 0, 0, 2, 1, 2>"): lets bench.py name its roofline kernel by the profiler's symbol.
- * htrvt_error_counts records its kernel here as well; a call that is refused leaves the value alone. */
+ * htrvt_error_counts records its kernel here as well, and htrvt_stem_fwd which of its three ("stem_mfma_fwd_kernel",
+ * "stem_fused_fwd_kernel<bf16_t>", "stem_fused_fwd_kernel<float>"); a call that is refused leaves the value alone. */
 const char* htrvt_last_kernel(void);
 
 /* One MFMA GEMM   C[m][n] = alpha * sum_k A(m,k) * B(n,k)  (+ epilogue).

@@ -229,6 +229,34 @@ def conv1_fwd(img, stats, w):
     return out, col.reshape(-1, 2, C)
 
 
+def stem_moments(img, stats):
+    """-> X [9], R [9][9]: the sum of each of the nine whitened, zero-padded taps over all conv output positions
+    (stride (2,1), pad 1) and the sums of their pairwise products"""
+    taps = F.unfold(whiten(img, stats)[:, None], 3, padding=1, stride=(2, 1))     # [B][9][Ho*W]
+    return taps.sum((0, 2)), torch.einsum("btp,bup->tu", taps, taps)
+
+
+def stem_colstats(img, stats, w):
+    """-> [2][C] = (sum, sum of squares) of the conv1 output per channel over the whole batch, from the image moments
+    alone: sum y_c = w_c . X, sum y_c^2 = w_c^T R w_c"""
+    X, Rm = stem_moments(img, stats)
+    return torch.stack([w @ X, torch.einsum("ct,tu,cu->c", w, Rm, w)])
+
+
+def stem_fwd(img, stats, w, scale, shift):
+    """conv1 -> BatchNorm (scale, shift) -> ReLU -> max-pool: y [B][Hp][W][C], idx uint8 as bn_relu_maxpool"""
+    return bn_relu_maxpool(conv1_fwd(img, stats, w)[0], scale, shift)
+
+
+def stem_f16_bound(img, stats, w, scale):
+    """-> [B][H/2][W][C]: bound on the error of the BatchNorm output when the scaled weights w[c][t] * scale[c] and the
+    whitened taps x_t are each rounded to float16 (relative 2^-11 each, so 2^-10 per product, second order dropped):
+    2^-10 * sum_t |w[c][t] scale[c]| |x_t|, the same convolution over absolute values"""
+    C = w.shape[0]
+    aw = (w * scale[:, None]).abs().view(C, 1, 3, 3)
+    return 2.0 ** -10 * F.conv2d(whiten(img, stats).abs()[:, None], aw, stride=(2, 1), padding=1).permute(0, 2, 3, 1).contiguous()
+
+
 def conv1_wgrad(img, stats, dy):
     """dy [B][H/2][W][C] -> dw [C][9] = sum over pixels of dy * whitened tap"""
     B, Ho, W, C = dy.shape

@@ -182,6 +182,42 @@ def test_conv1_references_match_autograd(u8):
     assert _close(dw2, dw, 1e-8) and _close(dgamma2, dgamma, 1e-9) and _close(dbeta2, dbeta, 1e-9)
 
 
+@pytest.mark.parametrize("u8", [False, True])
+@pytest.mark.parametrize("B,H,W", [(1, 2, 1), (2, 4, 4), (3, 10, 37)])
+def test_stem_references(B, H, W, u8):
+    """moments: an explicit loop over the nine zero-padded, strided taps; column statistics from the moments == conv1_fwd's
+    summed over its rows; the fused forward == ATen's conv2d -> relu -> max_pool2d; the float16 bound really bounds a
+    float64 evaluation over float16-rounded operands"""
+    g = torch.Generator().manual_seed(B * 100 + H + W)
+    C = 6
+    img = torch.randint(0, 256, (B, H, W), generator=g).to(torch.uint8) if u8 else torch.rand(B, H, W, generator=g, dtype=F64)
+    stats = R.img_stats(img.reshape(B, -1), 1e-5)
+    w = torch.randn(C, 9, generator=g, dtype=F64) * 0.3
+    xw = F.pad(R.whiten(img, stats), (1, 1, 1, 1))
+    Hc = H // 2
+    taps = torch.stack([xw[:, r:r + 2 * Hc:2, c:c + W] for r in range(3) for c in range(3)])      # [9][B][Hc][W]
+    X, Rm = R.stem_moments(img, stats)
+    assert X.shape == (9,) and Rm.shape == (9, 9)
+    assert _close(X, taps.sum((1, 2, 3)), 1e-12) and _close(Rm, torch.einsum("tbhw,ubhw->tu", taps, taps), 1e-12)
+    out, col = R.conv1_fwd(img, stats, w)
+    cs = R.stem_colstats(img, stats, w)
+    assert cs.shape == (2, C)
+    assert _close(cs[0], col[:, 0].sum(0), 1e-12) and _close(cs[1], col[:, 1].sum(0), 1e-12)
+    scale, shift = torch.randn(C, generator=g, dtype=F64) + 1, torch.randn(C, generator=g, dtype=F64) * 0.5
+    y, idx = R.stem_fwd(img, stats, w, scale, shift)
+    z = torch.relu(out * scale + shift).permute(0, 3, 1, 2)
+    assert torch.equal(y, F.max_pool2d(z, 3, stride=(2, 1), padding=1).permute(0, 2, 3, 1))
+    assert y.shape == (B, R.pooled_rows(Hc), W, C) and idx.dtype == torch.uint8 and torch.equal(idx == 15, ~(y > 0))
+    bound = R.stem_f16_bound(img, stats, w, scale)
+    assert bound.shape == out.shape
+    w16 = (w * scale[:, None]).to(torch.float16).to(F64)
+    x16 = R.whiten(img, stats).to(torch.float16).to(F64)
+    u16 = F.conv2d(x16[:, None], w16.view(C, 1, 3, 3), stride=(2, 1), padding=1).permute(0, 2, 3, 1) + shift
+    d = (u16 - (out * scale + shift)).abs()
+    assert (d <= bound * (1 + 2.0 ** -10) + 1e-12).all()
+    assert B * H * W < 32 or float((d / bound.clamp_min(1e-30)).max()) > 0.05      # and is no idle bound
+
+
 def test_e32_and_gate_helpers():
     x = torch.randn(64, 64, dtype=F64)
     (ref,), (err,) = R.e32(lambda a: a @ a, [x])
