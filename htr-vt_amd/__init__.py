@@ -10,6 +10,8 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from . import _lib  # noqa: F401,E402  (raises loudly when libhtrvt_hip.so is missing)
+from . import augment  # noqa: F401,E402
+from .augment import SameTrCollate  # noqa: F401,E402
 from .ctc import ctc_forward_backward, ctc_loss, greedy_decode  # noqa: F401,E402
 from .data import prepare_lines  # noqa: F401,E402
 from .ema import ModelEma  # noqa: F401,E402

@@ -127,6 +127,9 @@ PROTOTYPES = {
     "htrvt_adamw_dev": (i32, [vp, vp, vp, vp, i64, vp, vp]),
     "htrvt_line_max_scale": (i32, []),
     "htrvt_line_prepare": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "htrvt_aug_warp": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "htrvt_aug_morph": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "htrvt_aug_jitter": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "htrvt_ctc_workspace_floats": (C.c_size_t, [i32, i32, i32]),
     "htrvt_ctc_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "htrvt_sgm_context": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -476,6 +476,54 @@ int htrvt_line_max_scale(void);
 int htrvt_line_prepare(const uint8_t* src, const HtrvtLineImage* table, uint8_t* tmp, uint8_t* dst, int B, int H, int W,
                        int max_src_h, void* stream);
 
+/* ---- in front of the path: the train-time augmentation (csrc/augment.hip) --------------------------------
+ * data/dataset.py:13-45 (SameTrCollate): per batch three coins, and for each that lands heads one stage over every image.
+ * Each stage reads the uniform uint8 batch src [B][H][W] and writes dst [B][H][W] (another buffer: src == dst is refused);
+ * every random draw is made on the host and arrives in a device table; an image whose record is off is copied bit for bit.
+ * Refused before any launch (-1, reason in htrvt_last_error()): a null pointer, B / H / W < 1 or above the caps below, and
+ * for the morphology an effective extent above HTRVT_AUG_MAX_EXTENT.  The tables live in device memory and are not
+ * read on the host: no value in them makes a kernel read or write outside the two batches.
+ *
+ * htrvt_aug_warp: transform.py:151-224, skimage's warp(order 1, mode 'constant', cval 255) to an R x C image and its
+ *   resize(order 1, mode 'reflect') back to H x W, as one launch without the R x C image.  m = the normalised 3 x 3 map,
+ *   row-major, taking pixel (c, r) of the warped image to source coordinates (u / q, v / q), (u, v, q) = m (c, r, 1).
+ *   Output pixel (y, x): rr = (y + 0.5) * (R / H) - 0.5, cc likewise; floor and fraction; bilinear over four warped pixels
+ *   with indices clamped to [0, R-1] x [0, C-1]; each warped pixel bilinear over four source taps, a tap outside the image
+ *   = 255; both as (1-dr) * ((1-dc) * a + dc * b) + dr * ((1-dc) * c + dc * d) in float64 without fma; clamp to [0, 255],
+ *   truncate.  A source point that is not finite (or beyond 1e9) reads 255.  The anti-aliasing Gaussian of a shrinking
+ *   resize is left out: the host refuses plans with sigma = (R / H - 1) / 2 (or the column one) above 0.19.
+ * htrvt_aug_morph: transform.py:11-33, cv2.erode / cv2.dilate with np.ones((rows, cols)), `iterations` times, one set of
+ *   parameters for the batch; on int32 [B] (0 = copy).  cv2's conventions: anchor (rows / 2, cols / 2), the same offsets for
+ *   both operations, pixels outside the image ignored; iterating a full rectangle = one pass with extents
+ *   (k - 1) * iterations + 1 and the anchor times iterations, which is how it is run.  Exact.
+ * htrvt_aug_jitter: torchvision ColorJitter on a mode-L Pillow image, where only brightness and contrast act.  Both are
+ *   Pillow blends in float32, t = deg + f * (x - deg) as a rounded product then a rounded sum, truncated (0 <= f <= 1) or
+ *   clipped to [0, 255] and truncated; brightness: deg = 0; contrast: deg = (2 * sum + count) / (2 * count) in integers over
+ *   the image the contrast step receives (after brightness unless HTRVT_AUG_CONTRAST_FIRST).  Bit-exact against Pillow. */
+#define HTRVT_AUG_MAX_B 65535
+#define HTRVT_AUG_MAX_H 1024
+#define HTRVT_AUG_MAX_W 16384
+#define HTRVT_AUG_MAX_EXTENT 16          /* effective rows / cols of the morphology's rectangle */
+typedef struct HtrvtAugWarp {
+  double m[9];
+  int32_t rows, cols;                    /* R, C: shape of the warped image */
+  int32_t on;
+  int32_t reserved_;
+} HtrvtAugWarp;
+#define HTRVT_AUG_ON 1                   /* HtrvtAugJitter.flags */
+#define HTRVT_AUG_BRIGHTNESS 2           /* the brightness step acts (its strength is not 0) */
+#define HTRVT_AUG_CONTRAST 4
+#define HTRVT_AUG_CONTRAST_FIRST 8       /* the permutation puts contrast before brightness */
+typedef struct HtrvtAugJitter {
+  float brightness, contrast;            /* the two factors */
+  int32_t flags;
+  int32_t reserved_;
+} HtrvtAugJitter;
+int htrvt_aug_warp(const uint8_t* src, const HtrvtAugWarp* table, uint8_t* dst, int B, int H, int W, void* stream);
+int htrvt_aug_morph(const uint8_t* src, const int32_t* on, uint8_t* dst, int B, int H, int W, int rows, int cols,
+                    int iterations, int dilate, void* stream);
+int htrvt_aug_jitter(const uint8_t* src, const HtrvtAugJitter* table, uint8_t* dst, int B, int H, int W, void* stream);
+
 /* ---- the SGM forks' semantic-guidance head (csrc/sgm.hip; sgm_head.py of every model_sgm_ fork) ---------------------------
  * Row r of the head's query batch is (b, dir, l) of [B][2][L]: dir 0 = the left windows, 1 = the right windows.
  * htrvt_sgm_context: make_context_batch (:29-73).  table int32 = [B] offsets into the ids, [B] lengths, the packed ids;
