@@ -167,6 +167,19 @@ PROTOTYPES = {
     "htrvt_mixer_fwd_eval": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_mixer_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "htrvt_mixer_bwd": (i32, [vp] * 10 + [i32, i32, i32, i32, i32, vp]),
+    "htrvt_van_dw_fwd": (i32, [vp, vp, vp] + [i32] * 8 + [vp]),
+    "htrvt_van_dw_bwd_input": (i32, [vp, vp, vp, vp] + [i32] * 8 + [vp]),
+    "htrvt_van_dw_rows": (i32, [i32] * 8),
+    "htrvt_van_dw_bwd_workspace_floats": (i64, [i32] * 8),
+    "htrvt_van_dw_bwd_weight": (i32, [vp, vp, vp] + [i32] * 8 + [vp]),
+    "htrvt_van_moments_rows": (i32, [i64, i32, i32]),
+    "htrvt_van_moments": (i32, [vp, vp, i64, i32, i32, vp]),
+    "htrvt_van_gate_fwd": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_van_gate_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_van_bn_res_gelu_fwd": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_van_bn_res_gelu_bwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "htrvt_van_hpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_van_hpool_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
 }
 
 

@@ -1,9 +1,11 @@
-"""The launch sequences of the attention flavours, norms and the convolutional token mixer, each written once.
+"""The launch sequences of the attention flavours, norms, the convolutional token mixer and the VAN forks' height reducer
+and horizontal mixer, each written once.
 
 Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
 torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
-here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, and the autograd wrappers of variants.py.
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, and the autograd wrappers of
+variants.py.
 
 Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5.
 
@@ -32,12 +34,17 @@ def convert(src, dst, accumulate=False):
     return dst
 
 
-def linear_wgrad(dy, x, rows):
-    """a Linear's parameter gradients: dW [N, K] float32 = dy[rows, N]^T x[rows, K]; db [N] = column sums of dy"""
+def linear_wgrad(dy, x, rows, bias=True, split_k=1):
+    """a Linear's parameter gradients: dW [N, K] float32 = dy[rows, N]^T x[rows, K]; db [N] = column sums of dy (None
+    without `bias`).  split_k > 1: the rows are contracted in that many ranges, each into a float32 slab of its own, added in
+    order (reproducible; see wgrad_split_k)"""
     N, K = dy.shape[1], x.shape[1]
     dw = torch.zeros(N, K, dtype=torch.float32, device=dy.device)
+    ws = _f32(dy, split_k, N, K) if split_k > 1 else None
     gemm(dy, x, dw, dtype=dy.dtype, M=N, N=K, K=rows, lda=N, ldb=K, ldc=K, a_layout=MNMAJOR, b_layout=MNMAJOR,
-         accumulate=True, c_f32=True)
+         accumulate=True, c_f32=True, split_k=split_k, splitk_ws=ws)
+    if not bias:
+        return dw, None
     db = torch.zeros(N, dtype=torch.float32, device=dy.device)
     colsum(dy, rows, N, N, db, dti=dt(dy.dtype))
     return dw, db
@@ -418,3 +425,212 @@ def conv_mixer_bwd(ds, u, weight, B, N, saved, gamma=None, training=False, need_
         dbias = torch.zeros(D, dtype=torch.float32, device=u.device)
         colsum(pb, rows, D, D, dbias, dti=0)
     return du, dweight, dgamma, dbeta, dbias
+
+
+# ---- VAN forks (csrc/van.hip): VANBlock and HorizontalMixer of model_sgm_mms_attach_van/model/HTR_VT.py on NHWC ----------
+# Activations are x [B, H, W, C] (contiguous, float32 or bfloat16) and, for the 1x1 convolutions and the BatchNorm passes,
+# the same memory as rows [B*H*W, C].  Depthwise weights are the Conv2d parameters [C, 1, kh, kw] float32; the 1x1 weights
+# come as [C, C] in the activations' dtype.  A BatchNorm is bn = (gamma, beta, running_mean, running_var,
+# num_batches_tracked), all as stored; in training mode the three buffers are updated in place.
+
+def dwconv_fwd(x, weight, dilation=1):
+    """depthwise Conv2d(C, C, (kh, kw), padding = (k // 2) * dilation, dilation, groups = C, bias = False) of x NHWC"""
+    B, H, W, C = x.shape
+    kh, kw = weight.shape[-2:]
+    y = torch.empty_like(x)
+    check(lib.htrvt_van_dw_fwd(ptr(x), ptr(weight), ptr(y), B, H, W, C, kh, kw, dilation, dt(x.dtype), stream()), "van_dw_fwd")
+    return y
+
+
+def dwconv_bwd(dy, x, weight, dilation=1, add=None):
+    """(dx (+ add, a gradient that reaches x by another path), dweight float32 of weight's shape)"""
+    B, H, W, C = x.shape
+    kh, kw = weight.shape[-2:]
+    geo = (B, H, W, C, kh, kw, dilation, dt(x.dtype))
+    rows = lib.htrvt_van_dw_rows(*geo)
+    if rows < 0:
+        check(-1, "van_dw_rows")
+    dx = torch.empty_like(x)
+    check(lib.htrvt_van_dw_bwd_input(ptr(dy), ptr(weight), ptr(add), ptr(dx), *geo, stream()), "van_dw_bwd_input")
+    partial = _f32(x, rows, C * kh * kw)
+    check(lib.htrvt_van_dw_bwd_weight(ptr(x), ptr(dy), ptr(partial), *geo, stream()), "van_dw_bwd_weight")
+    dweight = torch.zeros_like(weight)
+    colsum(partial, rows, C * kh * kw, C * kh * kw, dweight, dti=0)
+    return dx, dweight
+
+
+def bn_coeffs(x, bn, training, eps, momentum):
+    """(scale, shift, mean, rstd) float32 [C] of BatchNorm2d over x [rows, C]: the batch statistics of x as stored (and the
+    running buffers updated) in training mode, else the running ones"""
+    rows, C = x.shape
+    gamma, beta, rmean, rvar, nbt = bn
+    scale, shift, mean, rstd = _f32(x, C), _f32(x, C), _f32(x, C), _f32(x, C)
+    if not training:
+        check(lib.htrvt_bn_eval_coeffs(ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), eps, ptr(scale), ptr(shift), ptr(rstd), C,
+                                       stream()), "bn_eval_coeffs")
+        return scale, shift, rmean.clone(), rstd
+    if rows < 2:
+        raise ValueError("BatchNorm in training mode needs more than one value per channel")
+    Q = lib.htrvt_van_moments_rows(rows, C, dt(x.dtype))
+    if Q < 0:
+        check(-1, "van_moments_rows")
+    partial = _f32(x, Q, 2, C)
+    check(lib.htrvt_van_moments(ptr(x), ptr(partial), rows, C, dt(x.dtype), stream()), "van_moments")
+    check(lib.htrvt_bn_finalize(ptr(partial), Q, C, float(rows), ptr(gamma), ptr(beta), eps, momentum, ptr(rmean), ptr(rvar),
+                                ptr(nbt), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), stream()), "bn_finalize")
+    return scale, shift, mean, rstd
+
+
+def bn_bwd(dz, x, gamma, mean, rstd, training):
+    """BatchNorm backward over [rows, C] on the htrvt_bn_bwd_* passes: dz the gradient of the output, x the input ->
+    (dx, dgamma, dbeta); eval mode: the statistics are constants"""
+    rows, C = x.shape
+    dti, st = dt(x.dtype), stream()
+    nblk = lib.htrvt_bn_bwd_blocks(rows)
+    partial, coef = _f32(x, nblk, 2, C), _f32(x, 3, C)
+    check(lib.htrvt_bn_bwd_reduce(ptr(dz), None, ptr(x), ptr(mean), ptr(rstd), ptr(partial), rows, C, dti, st), "bn_bwd_reduce")
+    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    check(lib.htrvt_bn_bwd_finalize(ptr(partial), nblk, C, float(rows) if training else 0.0, ptr(gamma), ptr(mean), ptr(rstd),
+                                    ptr(dgamma), ptr(dbeta), ptr(coef), st), "bn_bwd_finalize")
+    dx = torch.empty_like(x)
+    check(lib.htrvt_bn_bwd_apply(ptr(dz), None, ptr(x), ptr(coef), ptr(dx), None, rows, C, dti, st), "bn_bwd_apply")
+    return dx, dgamma, dbeta
+
+
+def wgrad_split_k(rows, N, K):
+    """split-K factor of a [N, K] weight gradient over `rows` rows: a power of two, ranges of at least 2048 rows, no more
+    (range, 256 x 192 tile) pairs than the 256 CUs -- a 768 x 768 gradient is 12 tiles, which alone would leave 244 CUs idle
+    over the 65 536 rows of the forks' map"""
+    tiles = ((N + 255) // 256) * ((K + 191) // 192)
+    sk = 1
+    while 2 * sk <= min(rows // 2048, 256 // tiles):
+        sk *= 2
+    return sk
+
+
+def _pw_wgrad(dy, x, bias=True):
+    """(dW, db) of a 1x1 convolution on rows"""
+    rows = dy.shape[0]
+    return linear_wgrad(dy, x, rows, bias=bias, split_k=wgrad_split_k(rows, dy.shape[1], x.shape[1]))
+
+
+def _pw(x, w, **kw):
+    """1x1 convolution of x [rows, C] with w [Cout, C]"""
+    rows, C = x.shape
+    y = _like(x, rows, w.shape[0])
+    gemm(x, w, y, dtype=x.dtype, M=rows, N=w.shape[0], K=C, lda=C, ldb=C, ldc=w.shape[0], **kw)
+    return y
+
+
+def _pw_dgrad(dy, w, **kw):
+    rows, N = dy.shape
+    dx = _like(dy, rows, w.shape[1])
+    gemm(dy, w, dx, dtype=dy.dtype, M=rows, N=w.shape[1], K=N, lda=N, ldb=w.shape[1], ldc=w.shape[1], b_layout=MNMAJOR, **kw)
+    return dx
+
+
+def lka_fwd(a, dw_w, dwd_w, pw_w, bn, training, eps, momentum):
+    """LargeKernelAttention on a [B, H, W, C]: a * bn(pw(dwd(dw(a)))), dw 5x5, dwd 7x7 dilation 3 -> (g, saved)"""
+    C = a.shape[-1]
+    d1 = dwconv_fwd(a, dw_w, 1)
+    d2 = dwconv_fwd(d1, dwd_w, 3)
+    p = _pw(d2.view(-1, C), pw_w)
+    scale, shift, mean, rstd = bn_coeffs(p, bn, training, eps, momentum)
+    g = torch.empty_like(p)
+    check(lib.htrvt_van_gate_fwd(ptr(a), ptr(p), ptr(scale), ptr(shift), ptr(g), p.shape[0], C, dt(a.dtype), stream()),
+          "van_gate_fwd")
+    return g, (d1, d2, p, scale, shift, mean, rstd)
+
+
+def lka_bwd(dg, a, dw_w, dwd_w, pw_w, gamma, saved, training):
+    """dg [rows, C] -> (da [B, H, W, C], {parameter gradients, float32})"""
+    d1, d2, p, scale, shift, mean, rstd = saved
+    rows, C = p.shape
+    da, dz = torch.empty_like(p), torch.empty_like(p)
+    check(lib.htrvt_van_gate_bwd(ptr(dg), ptr(a), ptr(p), ptr(scale), ptr(shift), ptr(da), ptr(dz), rows, C, dt(a.dtype),
+                                 stream()), "van_gate_bwd")
+    dp, dgamma, dbeta = bn_bwd(dz, p, gamma, mean, rstd, training)
+    dpw = _pw_wgrad(dp, d2.view(rows, C), bias=False)[0]
+    dd2 = _pw_dgrad(dp, pw_w).view(a.shape)
+    dd1, ddwd = dwconv_bwd(dd2, d1, dwd_w, 3)
+    da, ddw = dwconv_bwd(dd1, a, dw_w, 1, add=da.view(a.shape))
+    return da, {"dw.weight": ddw, "dwd.weight": ddwd, "pw.weight": dpw, "bn.weight": dgamma, "bn.bias": dbeta}
+
+
+def van_block_fwd(x, P, lka_bn, norm_bn, training, eps, momentum):
+    """VANBlock on x [B, H, W, C]: x + norm(proj2(lka(gelu(proj1(x))))).  P: the block's parameters by the fork's names,
+    the four 1x1 weights as [C, C] in x's dtype -> (y, saved)"""
+    C = x.shape[-1]
+    xr = x.view(-1, C)
+    pre = torch.empty_like(xr)
+    a = _pw(xr, P["proj1.weight"], bias=P["proj1.bias"], act=1, preact=pre).view(x.shape)
+    g, lka_saved = lka_fwd(a, P["lka.dw.weight"], P["lka.dwd.weight"], P["lka.pw.weight"], lka_bn, training, eps[0], momentum[0])
+    q = _pw(g, P["proj2.weight"], bias=P["proj2.bias"])
+    scale, shift, mean, rstd = bn_coeffs(q, norm_bn, training, eps[1], momentum[1])
+    y = torch.empty_like(x)
+    check(lib.htrvt_bn_apply(ptr(q), ptr(scale), ptr(shift), ptr(x), None, None, ptr(y), q.shape[0], C, 0, dt(x.dtype),
+                             stream()), "bn_apply")
+    return y, (pre, a, g, q, mean, rstd) + lka_saved
+
+
+def van_block_bwd(dy, x, P, saved, training):
+    """dy [B, H, W, C] -> (dx, {parameter gradients by the fork's names, float32})"""
+    pre, a, g, q, mean, rstd, *lka_saved = saved
+    rows, C = q.shape
+    dyr = dy.view(rows, C)
+    dq, dgamma, dbeta = bn_bwd(dyr, q, P["norm.weight"], mean, rstd, training)
+    dw2, db2 = _pw_wgrad(dq, g)
+    dg = _pw_dgrad(dq, P["proj2.weight"])
+    da, grads = lka_bwd(dg, a, P["lka.dw.weight"], P["lka.dwd.weight"], P["lka.pw.weight"], P["lka.bn.weight"], lka_saved,
+                        training)
+    dpre = torch.empty_like(pre)
+    check(lib.htrvt_van_bn_res_gelu_bwd(ptr(da), ptr(pre), None, None, None, ptr(dpre), rows, C, dt(x.dtype), stream()),
+          "van_bn_res_gelu_bwd")
+    dw1, db1 = _pw_wgrad(dpre, x.view(rows, C))
+    dx = _pw_dgrad(dpre, P["proj1.weight"], residual=dyr).view(x.shape)
+    grads = {"lka." + k: v for k, v in grads.items()}
+    grads.update({"proj1.weight": dw1, "proj1.bias": db1, "proj2.weight": dw2, "proj2.bias": db2, "norm.weight": dgamma,
+                  "norm.bias": dbeta})
+    return dx, grads
+
+
+def hmixer_fwd(x, dw_w, pw_w, bn, training, eps, momentum):
+    """HorizontalMixer on x [B, 1, W, C]: gelu(x + bn(pw(dw(x)))), dw 1 x k -> (y, saved)"""
+    C = x.shape[-1]
+    d = dwconv_fwd(x, dw_w, 1)
+    p = _pw(d.view(-1, C), pw_w)
+    scale, shift, mean, rstd = bn_coeffs(p, bn, training, eps, momentum)
+    y = torch.empty_like(x)
+    check(lib.htrvt_van_bn_res_gelu_fwd(ptr(p), ptr(scale), ptr(shift), ptr(x), ptr(y), p.shape[0], C, dt(x.dtype), stream()),
+          "van_bn_res_gelu_fwd")
+    return y, (d, p, scale, shift, mean, rstd)
+
+
+def hmixer_bwd(dy, x, dw_w, pw_w, gamma, saved, training):
+    """dy [B, 1, W, C] -> (dx, {parameter gradients, float32})"""
+    d, p, scale, shift, mean, rstd = saved
+    rows, C = p.shape
+    dt_ = torch.empty_like(p)
+    check(lib.htrvt_van_bn_res_gelu_bwd(ptr(dy), ptr(p), ptr(scale), ptr(shift), ptr(x), ptr(dt_), rows, C, dt(x.dtype),
+                                        stream()), "van_bn_res_gelu_bwd")
+    dp, dgamma, dbeta = bn_bwd(dt_, p, gamma, mean, rstd, training)
+    dpw = _pw_wgrad(dp, d.view(rows, C), bias=False)[0]
+    dd = _pw_dgrad(dp, pw_w).view(x.shape)
+    dx, ddw = dwconv_bwd(dd, x, dw_w, 1, add=dt_.view(x.shape))
+    return dx, {"dw.weight": ddw, "pw.weight": dpw, "bn.weight": dgamma, "bn.bias": dbeta}
+
+
+def height_pool_fwd(x):
+    """x [B, H, W, C] -> the mean over H, [B, W, C]"""
+    B, H, W, C = x.shape
+    y = _like(x, B, W, C)
+    check(lib.htrvt_van_hpool_fwd(ptr(x), ptr(y), B, H, W, C, dt(x.dtype), stream()), "van_hpool_fwd")
+    return y
+
+
+def height_pool_bwd(d, H):
+    """d [B, W, C] -> d / H broadcast to [B, H, W, C]"""
+    B, W, C = d.shape
+    dx = _like(d, B, H, W, C)
+    check(lib.htrvt_van_hpool_bwd(ptr(d), ptr(dx), B, H, W, C, dt(d.dtype), stream()), "van_hpool_bwd")
+    return dx

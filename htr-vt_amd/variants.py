@@ -5,7 +5,8 @@ and SGM head (sgm/model/sgm_head.py) call the same seq_ops functions directly, s
 below exercises the launch sequence the models run.  Wrapped: the window fork's relative-position attention (table
 -driven in bfloat16; in float32 ONE dense bias [heads, N, N], table entries inside a window and MASKED outside, into the
 batched-GEMM route), the SGM head's single-head cross-attention, the LGP block's window-12 attention, pool + norm
-and scaled up-sampling, the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU, and the forks' regularisers
+and scaled up-sampling, the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU, the VAN forks' depthwise
+Conv2d (depthwise_conv2d), and the forks' regularisers
 as operators: dropout on the attention probabilities (self_attention, relpos_self_attention(dropout_p=...)) and
 residual + drop_path(dropout(x)) (residual_dropout); wiring those into the models is not done here.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
 run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
@@ -423,3 +424,34 @@ def glu_dwconv_bn_silu(u, weight, bn_weight, bn_bias, running_mean, running_var,
         raise ValueError("glu_dwconv_bn_silu: either BatchNorm (weight, bias, running buffers) or a convolution bias")
     return _GluDwconvBnSilu.apply(u, weight, bn_weight, bn_bias, conv_bias, running_mean, running_var, num_batches_tracked,
                                   B, N, bool(training), float(eps), float(momentum))
+
+
+# ---- VAN forks (model_sgm_mms_attach_van/model/HTR_VT.py LargeKernelAttention / HorizontalMixer): depthwise Conv2d, csrc/van.hip
+
+class _DepthwiseConv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, dilation):
+        x, weight = x.contiguous(), weight.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.dilation = dilation
+        return seq_ops.dwconv_fwd(x, weight, dilation)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx, dweight = seq_ops.dwconv_bwd(dy.contiguous().to(x.dtype), x, weight, ctx.dilation)
+        return dx, dweight, None
+
+
+def depthwise_conv2d(x_nhwc, weight, dilation=1):
+    """nn.Conv2d(C, C, (kh, kw), padding=((kh // 2) * dilation, (kw // 2) * dilation), dilation=dilation, groups=C,
+    bias=False) on x_nhwc [B, H, W, C] (float32 or bfloat16, C a multiple of 8) -> [B, H, W, C].  weight: the Conv2d's
+    float32 [C, 1, kh, kw], kh odd <= 7, kw odd <= 9, dilation 1 ... 3; zero padding per image.  Differentiable in x_nhwc and
+    weight; the gradients are bitwise reproducible."""
+    _need_device(x_nhwc, weight)
+    if weight.dtype != torch.float32:
+        raise TypeError(f"depthwise_conv2d: float32 weight expected (the parameter as stored), got {weight.dtype}")
+    if x_nhwc.dim() != 4 or weight.dim() != 4 or weight.shape[0] != x_nhwc.shape[3] or weight.shape[1] != 1:
+        raise ValueError(f"depthwise_conv2d: x [B, H, W, C] and weight [C, 1, kh, kw] expected, got {tuple(x_nhwc.shape)} "
+                         f"and {tuple(weight.shape)}")
+    return _DepthwiseConv2d.apply(x_nhwc, weight, int(dilation))

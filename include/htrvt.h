@@ -645,6 +645,63 @@ int htrvt_mixer_bwd(const void* u, const void* c, const void* ds, const float* w
                     const float* coef, void* du, float* dw_partial, float* db_partial, int B, int N, int D, int k, int dtype,
                     void* stream);
 
+/* The VAN forks' height reducer and horizontal mixer (model_sgm_mms_attach_van/model/HTR_VT.py:159-254 LargeKernelAttention,
+ * VANBlock, VANHeightReducer, HorizontalMixer; model_sgm_mms_attach_van_2 is identical): what they need beside the 1x1
+ * convolutions (htrvt_gemm on the [B*H*W][C] rows) and the BatchNorm passes (htrvt_bn_*), csrc/van.hip.
+ * Tensors are NHWC [B][H][W][C] of type dtype (float32 or bfloat16), C a multiple of 8, 16-byte aligned; per-channel vectors
+ * and all weights are float32; sums are formed in float32 and a result is rounded once.  Depthwise weights are as torch
+ * stores them, w [C][kh * kw] (Conv2d.weight [C][1][kh][kw], groups = C), no re-layout.
+ *
+ * Depthwise convolution, kh in {1,3,5,7}, kw in {1,3,5,7,9}, dil in 1 ... 3 (the forks: 5x5 d1, 7x7 d3, 1x9 d1):
+ *   y[b][h][w][c] = sum_{i,j} w[c][i * kw + j] * x[b][h + (i - kh/2) * dil][w + (j - kw/2) * dil][c],
+ * a term whose row leaves 0 .. H-1 or whose column leaves 0 .. W-1 of ITS OWN image being zero (zero padding per image: no
+ * pixel of another image and nothing outside the buffer is read).  A kernel row i whose input row lies outside the image
+ * for output row h is skipped as a whole -- no loads, no multiply-adds -- by a test that is uniform over the workgroup;
+ * with H = 4 and dil = 3 at most 2 of 7 kernel rows are live.
+ *   htrvt_van_dw_fwd         y from x.
+ *   htrvt_van_dw_bwd_input   dx[b][h][w][c] = sum_{i,j} w[c][i * kw + j] * dy[b][h - (i - kh/2) * dil][w - (j - kw/2) * dil][c]
+ *                            (+ add[b][h][w][c] where add != NULL: a gradient that reaches x by another path): dy convolved
+ *                            with the flipped taps, same dilation, same skip of dead rows.
+ *   htrvt_van_dw_bwd_weight  partial [R][C * kh * kw] float32, R = htrvt_van_dw_rows(...): the rows sum (htrvt_colsum over
+ *                            C * kh * kw columns) to d w[c][i * kw + j] = sum_{b,h,w} dy[b][h][w][c] * x[b][h + (i - kh/2) *
+ *                            dil][w + (j - kw/2) * dil][c]; every element of every row is written.
+ *   htrvt_van_dw_bwd_workspace_floats  R * C * kh * kw.
+ * Passes over rows = B * H * W pixels, [rows][C]; scale == NULL stands for 1, shift == NULL for 0:
+ *   htrvt_van_moments        partial [Q][2][C] = (sum x, sum x^2) of the stored values, Q = htrvt_van_moments_rows(rows, C,
+ *                            dtype) <= 128, for htrvt_bn_finalize(partial, Q, C, count = rows, ...).
+ *   htrvt_van_gate_fwd       LKA gate g = a * (p * scale + shift): a the block's GELU output (the fork's u), p the pw
+ *                            convolution's output, scale / shift its BatchNorm's (htrvt_bn_finalize or htrvt_bn_eval_coeffs).
+ *   htrvt_van_gate_bwd       from dg: da = dg * (p * scale + shift), the part of d a through the gate's first factor, and
+ *                            dz = dg * a, the gradient of the BatchNorm output, laid out as htrvt_bn_bwd_reduce and
+ *                            htrvt_bn_bwd_apply take it.
+ *   htrvt_van_bn_res_gelu_fwd  y = gelu(res + x * scale + shift), exact (erf) GELU; res == NULL: without the shortcut.
+ *   htrvt_van_bn_res_gelu_bwd  dt = dy * gelu'(res + x * scale + shift), recomputed from x, scale, shift, res: the gradient
+ *                            of the shortcut and of the BatchNorm output.
+ * Height pool: htrvt_van_hpool_fwd  y[b][w][c] = mean_h x[b][h][w][c]; htrvt_van_hpool_bwd  dx[b][h][w][c] = d[b][w][c] / H.
+ * Every reduction is per-workgroup partial rows plus an ordered second stage (no float atomics): the gradients are bitwise
+ * reproducible.  Refused (negative return, htrvt_last_error(), nothing launched): kh / kw even or outside the set, dil outside
+ * 1 ... 3, C not a multiple of 8, a tensor that is not 16-byte aligned, a null required pointer, B * H > 65535. */
+int htrvt_van_dw_fwd(const void* x, const float* w, void* y, int B, int H, int W, int C, int kh, int kw, int dil, int dtype,
+                     void* stream);
+int htrvt_van_dw_bwd_input(const void* dy, const float* w, const void* add, void* dx, int B, int H, int W, int C, int kh,
+                           int kw, int dil, int dtype, void* stream);
+int htrvt_van_dw_rows(int B, int H, int W, int C, int kh, int kw, int dil, int dtype);
+int64_t htrvt_van_dw_bwd_workspace_floats(int B, int H, int W, int C, int kh, int kw, int dil, int dtype);
+int htrvt_van_dw_bwd_weight(const void* x, const void* dy, float* partial, int B, int H, int W, int C, int kh, int kw, int dil,
+                            int dtype, void* stream);
+int htrvt_van_moments_rows(int64_t rows, int C, int dtype);
+int htrvt_van_moments(const void* x, float* partial, int64_t rows, int C, int dtype, void* stream);
+int htrvt_van_gate_fwd(const void* a, const void* p, const float* scale, const float* shift, void* g, int64_t rows, int C,
+                       int dtype, void* stream);
+int htrvt_van_gate_bwd(const void* dg, const void* a, const void* p, const float* scale, const float* shift, void* da,
+                       void* dz, int64_t rows, int C, int dtype, void* stream);
+int htrvt_van_bn_res_gelu_fwd(const void* x, const float* scale, const float* shift, const void* res, void* y, int64_t rows,
+                              int C, int dtype, void* stream);
+int htrvt_van_bn_res_gelu_bwd(const void* dy, const void* x, const float* scale, const float* shift, const void* res, void* dt,
+                              int64_t rows, int C, int dtype, void* stream);
+int htrvt_van_hpool_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+int htrvt_van_hpool_bwd(const void* d, void* dx, int B, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
