@@ -180,6 +180,10 @@ PROTOTYPES = {
     "htrvt_van_bn_res_gelu_bwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "htrvt_van_hpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_van_hpool_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_attn_win2d_supported": (i32, [i32, i32, i32, i32]),
+    "htrvt_attn_win2d_fwd": (i32, [vp, vp, vp] + [i32] * 9 + [f32, i32, vp]),
+    "htrvt_attn_win2d_rows": (i32, [i32] * 6),
+    "htrvt_attn_win2d_bwd": (i32, [vp] * 5 + [i32] * 9 + [f32, i32, vp]),
 }
 
 

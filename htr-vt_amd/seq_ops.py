@@ -1,10 +1,10 @@
-"""The launch sequences of the attention flavours, norms, the convolutional token mixer and the VAN forks' height reducer
-and horizontal mixer, each written once.
+"""The launch sequences of the attention flavours, norms, the convolutional token mixer, the VAN forks' height reducer
+and horizontal mixer and the Swin fork's blocks, each written once.
 
 Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
 torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
-here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, and the autograd wrappers of
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, swin.py, and the autograd wrappers of
 variants.py.
 
 Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5.
@@ -634,3 +634,151 @@ def height_pool_bwd(d, H):
     dx = _like(d, B, H, W, C)
     check(lib.htrvt_van_hpool_bwd(ptr(d), ptr(dx), B, H, W, C, dt(d.dtype), stream()), "van_hpool_bwd")
     return dx
+
+
+# ---- Swin fork (csrc/swin.hip): WindowAttention2D, SwinBlock2D, HeightOnlyPatchMerging and Combining of ------------------
+# model_sgm_mms_swin/model/HTR_VT.py.  Activations are rows [B*H*W, C] in plain token order (b, h, w), float32 or bfloat16;
+# P holds a module's parameters by the fork's names, the Linear / Conv2d weights as [out, in] in the activations' dtype and
+# everything else float32 as stored.  Only the attention is a kernel of its own: the rest is layernorm_fwd / _bwd, the
+# GEMM with its bias / GELU / residual epilogues, linear_wgrad, the element-wise GELU backward and height_pool_fwd / _bwd.
+
+def win2d_attention_fwd(qkv, table, B, H, W, h, window, shift):
+    """attention inside window = (wh, ww) windows of the [H, W] token map rolled by -shift, with the bias of `table`
+    (float32 [(2wh-1)(2ww-1), h]) and the fork's additive -100 mask between the wrapped regions -> out [B*H*W, D]"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * H * W, D)
+    check(lib.htrvt_attn_win2d_fwd(ptr(qkv), ptr(table), ptr(out), B, H, W, h, hd, window[0], window[1], shift[0], shift[1],
+                                   hd ** -0.5, dt(qkv.dtype), stream()), "attn_win2d_fwd")
+    return out
+
+
+def win2d_attention_bwd(qkv, table, dout, B, H, W, h, window, shift, dtable=None):
+    """dqkv by the recomputing backward; dtable (float32, the table's shape) += the kernel's partial rows, added in row
+    order, None: the table gradient is dropped.  The rows are at most 256 and a table has any number of entries (630 in
+    the fork; htrvt_colsum takes columns in fours), so they go through htrvt_rowsum_f32, the ordered row sum that is
+    htrvt_colsum's own second stage"""
+    hd = _heads(qkv, h)[1]
+    rows = lib.htrvt_attn_win2d_rows(B, H, W, h, window[0], window[1])
+    if rows < 0:
+        check(-1, "attn_win2d_rows")
+    dqkv = torch.empty_like(qkv)
+    partial = _f32(qkv, rows, table.numel())
+    check(lib.htrvt_attn_win2d_bwd(ptr(qkv), ptr(table), ptr(dout), ptr(dqkv), ptr(partial), B, H, W, h, hd, window[0],
+                                   window[1], shift[0], shift[1], hd ** -0.5, dt(qkv.dtype), stream()), "attn_win2d_bwd")
+    if dtable is not None:
+        check(lib.htrvt_rowsum_f32(ptr(partial), rows, table.numel(), ptr(dtable), stream()), "rowsum_f32")
+    return dqkv
+
+
+def _gelu_bwd(dy, pre):
+    """dy * gelu'(pre), exact (erf) GELU"""
+    dpre = torch.empty_like(pre)
+    check(lib.htrvt_van_bn_res_gelu_bwd(ptr(dy), ptr(pre), None, None, None, ptr(dpre), pre.shape[0], pre.shape[1], dt(pre.dtype),
+                                        stream()), "van_bn_res_gelu_bwd")
+    return dpre
+
+
+def _ln_bwd(dy, x, mean, rstd, gamma, dres=None):
+    """(dx (+ dres), dgamma, dbeta)"""
+    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    return layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=dres), dgamma, dbeta
+
+
+def swin_block_fwd(x, P, B, H, W, h, window, shift, eps=1e-5, save=True):
+    """SwinBlock2D on x [B*H*W, C]: x1 = x + proj(attention(qkv(norm1(x)))), y = x1 + mlp.3(gelu(mlp.0(norm2(x1)))) ->
+    (y, saved)"""
+    n1, mean1, rstd1 = layernorm_fwd(x, P["norm1.weight"], P["norm1.bias"], eps, save)
+    qkv = _pw(n1, P["attn.qkv.weight"], bias=P["attn.qkv.bias"])
+    a = win2d_attention_fwd(qkv, P["attn.relative_position_bias_table"], B, H, W, h, window, shift)
+    x1 = _pw(a, P["attn.proj.weight"], bias=P["attn.proj.bias"], residual=x)
+    n2, mean2, rstd2 = layernorm_fwd(x1, P["norm2.weight"], P["norm2.bias"], eps, save)
+    pre = _like(x, x.shape[0], P["mlp.0.weight"].shape[0])
+    hid = _pw(n2, P["mlp.0.weight"], bias=P["mlp.0.bias"], act=1, preact=pre)
+    y = _pw(hid, P["mlp.3.weight"], bias=P["mlp.3.bias"], residual=x1)
+    return y, (n1, mean1, rstd1, qkv, a, x1, n2, mean2, rstd2, pre, hid)
+
+
+def swin_block_bwd(dy, x, P, saved, B, H, W, h, window, shift):
+    """dy [B*H*W, C] -> (dx, {parameter gradients by the fork's names, float32})"""
+    n1, mean1, rstd1, qkv, a, x1, n2, mean2, rstd2, pre, hid = saved
+    G = {}
+    G["mlp.3.weight"], G["mlp.3.bias"] = _pw_wgrad(dy, hid)
+    dpre = _gelu_bwd(_pw_dgrad(dy, P["mlp.3.weight"]), pre)
+    G["mlp.0.weight"], G["mlp.0.bias"] = _pw_wgrad(dpre, n2)
+    dx1, G["norm2.weight"], G["norm2.bias"] = _ln_bwd(_pw_dgrad(dpre, P["mlp.0.weight"]), x1, mean2, rstd2, P["norm2.weight"],
+                                                      dres=dy)
+    G["attn.proj.weight"], G["attn.proj.bias"] = _pw_wgrad(dx1, a)
+    table = P["attn.relative_position_bias_table"]
+    G["attn.relative_position_bias_table"] = torch.zeros_like(table)
+    dqkv = win2d_attention_bwd(qkv, table, _pw_dgrad(dx1, P["attn.proj.weight"]), B, H, W, h, window, shift,
+                               dtable=G["attn.relative_position_bias_table"])
+    G["attn.qkv.weight"], G["attn.qkv.bias"] = _pw_wgrad(dqkv, n1)
+    dx, G["norm1.weight"], G["norm1.bias"] = _ln_bwd(_pw_dgrad(dqkv, P["attn.qkv.weight"]), x, mean1, rstd1, P["norm1.weight"],
+                                                     dres=dx1)
+    return dx, G
+
+
+def _row_planes(x, B, H, W):
+    """x [B*H*W, C], H even -> the rows of the even and of the odd map rows, each [B*(H/2)*W, C] (strided copies)"""
+    C = x.shape[1]
+    x5 = x.view(B, H // 2, 2, W, C)
+    return x5[:, :, 0].contiguous().view(-1, C), x5[:, :, 1].contiguous().view(-1, C)
+
+
+def patch_merge_fwd(x, P, B, H, W, eps=1e-5, save=True):
+    """HeightOnlyPatchMerging on x [B*H*W, C]: norm(W0 x[b, 2h', w] + W1 x[b, 2h' + 1, w]), the Conv2d(C, Cout, (2, 1),
+    stride (2, 1), bias=False) as two products over the gathered even / odd map rows, the second taking the first as its
+    residual.  P["reduce.weight"]: (W0, W1), each [Cout, C] -> (y [B*(H/2)*W, Cout], saved)"""
+    xe, xo = _row_planes(x, B, H, W)
+    w0, w1 = P["reduce.weight"]
+    z = _pw(xo, w1, residual=_pw(xe, w0))
+    y, mean, rstd = layernorm_fwd(z, P["norm.weight"], P["norm.bias"], eps, save)
+    return y, (xe, xo, z, mean, rstd)
+
+
+def patch_merge_bwd(dy, P, saved, B, H, W):
+    """dy [B*(H/2)*W, Cout] -> (dx [B*H*W, C], {"reduce.weight": float32 [Cout, C, 2, 1], "norm.weight", "norm.bias"})"""
+    xe, xo, z, mean, rstd = saved
+    w0, w1 = P["reduce.weight"]
+    dz, dgamma, dbeta = _ln_bwd(dy, z, mean, rstd, P["norm.weight"])
+    dw = torch.stack((_pw_wgrad(dz, xe, bias=False)[0], _pw_wgrad(dz, xo, bias=False)[0]), dim=2).unsqueeze(3)
+    C = xe.shape[1]
+    dx = torch.stack((_pw_dgrad(dz, w0).view(B, H // 2, W, C), _pw_dgrad(dz, w1).view(B, H // 2, W, C)), dim=2)
+    return dx.view(B * H * W, C), {"reduce.weight": dw, "norm.weight": dgamma, "norm.bias": dbeta}
+
+
+def combining_fwd(x, P, B, H, W):
+    """Combining on x [B*H*W, C]: gelu(fc(mean over H)) -> (y [B*W, Cout], saved)"""
+    pooled = height_pool_fwd(x.view(B, H, W, x.shape[1])).view(B * W, x.shape[1])
+    pre = _like(x, B * W, P["fc.weight"].shape[0])
+    y = _pw(pooled, P["fc.weight"], bias=P["fc.bias"], act=1, preact=pre)
+    return y, (pooled, pre)
+
+
+def combining_bwd(dy, P, saved, B, H, W):
+    """dy [B*W, Cout] -> (dx [B*H*W, C], {"fc.weight", "fc.bias"})"""
+    pooled, pre = saved
+    dpre = _gelu_bwd(dy, pre)
+    dw, db = _pw_wgrad(dpre, pooled)
+    dx = height_pool_bwd(_pw_dgrad(dpre, P["fc.weight"]).view(B, W, pooled.shape[1]), H)
+    return dx.view(B * H * W, pooled.shape[1]), {"fc.weight": dw, "fc.bias": db}
+
+
+def window_attention_fwd(x, P, Bn, h, window):
+    """WindowAttention2D on partitioned windows x [Bn*wh*ww, C] without a mask: proj(attention(qkv(x))), every window a map
+    of its own -> (y, saved)"""
+    qkv = _pw(x, P["qkv.weight"], bias=P["qkv.bias"])
+    a = win2d_attention_fwd(qkv, P["relative_position_bias_table"], Bn, window[0], window[1], h, window, (0, 0))
+    return _pw(a, P["proj.weight"], bias=P["proj.bias"]), (qkv, a)
+
+
+def window_attention_bwd(dy, x, P, saved, Bn, h, window):
+    qkv, a = saved
+    G = {}
+    G["proj.weight"], G["proj.bias"] = _pw_wgrad(dy, a)
+    table = P["relative_position_bias_table"]
+    G["relative_position_bias_table"] = torch.zeros_like(table)
+    dqkv = win2d_attention_bwd(qkv, table, _pw_dgrad(dy, P["proj.weight"]), Bn, window[0], window[1], h, window, (0, 0),
+                               dtable=G["relative_position_bias_table"])
+    G["qkv.weight"], G["qkv.bias"] = _pw_wgrad(dqkv, x)
+    return _pw_dgrad(dqkv, P["qkv.weight"]), G

@@ -6,7 +6,7 @@ below exercises the launch sequence the models run.  Wrapped: the window fork's 
 -driven in bfloat16; in float32 ONE dense bias [heads, N, N], table entries inside a window and MASKED outside, into the
 batched-GEMM route), the SGM head's single-head cross-attention, the LGP block's window-12 attention, pool + norm
 and scaled up-sampling, the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU, the VAN forks' depthwise
-Conv2d (depthwise_conv2d), and the forks' regularisers
+Conv2d (depthwise_conv2d), the Swin fork's 2-D shifted-window attention (window_attention_2d), and the forks' regularisers
 as operators: dropout on the attention probabilities (self_attention, relpos_self_attention(dropout_p=...)) and
 residual + drop_path(dropout(x)) (residual_dropout); wiring those into the models is not done here.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
 run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
@@ -455,3 +455,48 @@ def depthwise_conv2d(x_nhwc, weight, dilation=1):
         raise ValueError(f"depthwise_conv2d: x [B, H, W, C] and weight [C, 1, kh, kw] expected, got {tuple(x_nhwc.shape)} "
                          f"and {tuple(weight.shape)}")
     return _DepthwiseConv2d.apply(x_nhwc, weight, int(dilation))
+
+
+# ---- Swin fork (model_sgm_mms_swin/model/HTR_VT.py WindowAttention2D inside SwinBlock2D): 2-D shifted windows, csrc/swin.hip
+
+class _WindowAttention2D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, B, H, W, heads, window, shift):
+        qkv, table = qkv.contiguous(), table.contiguous()
+        ctx.save_for_backward(qkv, table)
+        ctx.dims = (B, H, W, heads, window, shift)
+        return seq_ops.win2d_attention_fwd(qkv, table, *ctx.dims)
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, table = ctx.saved_tensors
+        dtable = torch.zeros_like(table) if ctx.needs_input_grad[1] else None
+        dqkv = seq_ops.win2d_attention_bwd(qkv, table, dout.contiguous().to(qkv.dtype), *ctx.dims, dtable=dtable)
+        return (dqkv, dtable) + (None,) * 6
+
+
+def win2d_supported(head_dim, window, dtype):
+    return bool(lib.htrvt_attn_win2d_supported(head_dim, window[0], window[1], dt(dtype)))
+
+
+def window_attention_2d(qkv, table, B, H, W, heads, window, shift=(0, 0)):
+    """WindowAttention2D as SwinBlock2D calls it, on its qkv Linear's output: qkv [B*H*W, 3*heads*hd] (float32 or
+    bfloat16, hd 32 / 64 / 128) in plain token order -> [B*H*W, heads*hd], attention inside the window = (wh, ww) windows
+    (wh * ww <= 32) of the map rolled by -shift, with the bias of table (the float32 parameter [(2wh-1)(2ww-1), heads])
+    and the fork's additive -100 mask between the wrapped regions.  Differentiable in qkv and table; the gradients are
+    bitwise reproducible."""
+    _need_device(qkv, table)
+    if table.dtype != torch.float32:
+        raise TypeError(f"window_attention_2d: float32 table expected (the parameter as stored), got {table.dtype}")
+    window, shift = tuple(int(v) for v in window), tuple(int(v) for v in shift)
+    entries = (2 * window[0] - 1) * (2 * window[1] - 1)
+    # the kernels see pointers only: a shape that disagrees with (B, H, W, heads, window) would send them past a buffer
+    if qkv.dim() != 2 or heads < 1 or qkv.shape[0] != B * H * W or qkv.shape[1] % (3 * heads):
+        raise ValueError(f"window_attention_2d: qkv [B*H*W = {B * H * W}, 3*heads*hd] expected for heads = {heads}, got "
+                         f"{tuple(qkv.shape)}")
+    if tuple(table.shape) != (entries, heads):
+        raise ValueError(f"window_attention_2d: table [(2wh-1)(2ww-1) = {entries}, heads = {heads}] expected for window "
+                         f"{window}, got {tuple(table.shape)}")
+    if not win2d_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype):
+        raise ValueError(f"window attention: {lib.htrvt_last_error().decode()}")
+    return _WindowAttention2D.apply(qkv, table, B, H, W, heads, window, shift)

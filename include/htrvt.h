@@ -702,6 +702,34 @@ int htrvt_van_bn_res_gelu_bwd(const void* dy, const void* x, const float* scale,
 int htrvt_van_hpool_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 int htrvt_van_hpool_bwd(const void* d, void* dx, int B, int H, int W, int C, int dtype, void* stream);
 
+/* ---- Swin fork (csrc/swin.hip): WindowAttention2D inside SwinBlock2D of model_sgm_mms_swin/model/HTR_VT.py, between the
+ * qkv and proj Linear layers: attention in 2-D windows of wh x ww <= 32 tokens of an H x W token map, with the learned
+ * relative-position bias, the 2-D cyclic shift and the fork's additive mask across the wrap.
+ *   qkv [B H W][3][heads][hd] in plain token order (b, h, w), as the qkv GEMM leaves it; out [B H W][heads][hd] and dqkv in
+ *   that same order; table float32 [(2wh-1)(2ww-1)][heads], the parameter as stored.  Roll, window partition, window reverse
+ *   and roll-back are index arithmetic: window (i, j), i < H / wh, j < W / ww, slot t = r ww + c sits at the shifted
+ *   coordinate (hs, ws) = (i wh + r, j ww + c) and reads qkv / writes out and dqkv at token ((hs + sh) mod H, (ws + sw) mod W)
+ *   -- torch.roll(x, (-sh, -sw)) before the partition and roll(.., (sh, sw)) after the merge.
+ *   S[t][u] = scale q_t.k_u + table[(r_t - r_u + wh - 1)(2ww - 1) + (c_t - c_u + ww - 1)][head] + m(t, u), softmax over u,
+ *   out_t = sum_u P[t][u] v_u.  m is SwinBlock2D._build_attn_mask: the region of a slot is the pair (sh > 0 and hs >= H - sh,
+ *   sw > 0 and ws >= W - sw) -- TWO regions per shifted axis, not standard Swin's three -- and m = -100.0 where the regions
+ *   of t and u differ, else 0.  The mask is ADDED: a masked pair whose raw score lies more than 100 above the rest still wins.
+ *   _bwd saves nothing but qkv: it recomputes the window's softmax, writes dqkv whole, and writes the table gradient as
+ *   partial rows, dtable_partial float32 [htrvt_attn_win2d_rows(..)][(2wh-1)(2ww-1) heads]: row p is the ordered sum of
+ *   dS[t][u] (the gradient of the pre-softmax score, without `scale`) into the table entry of (t, u) over the p-th share of
+ *   the B (H / wh)(W / ww) (image, window) items.  The rows (at most 256) are added by htrvt_rowsum_f32, htrvt_colsum's ordered
+ *   second stage (htrvt_colsum itself takes columns in fours; the fork's table has 630 entries).  No float atomics: two runs
+ *   give the same bits.
+ *   Served: float32 and bfloat16, hd 32 / 64 / 128, wh, ww >= 1 with wh ww <= 32, H % wh == 0, W % ww == 0, 0 <= sh < wh,
+ *   0 <= sw < ww, base pointers 16-byte aligned.  Everything else: a non-zero return, the reason in htrvt_last_error(),
+ *   nothing launched.  _supported: 1 if (hd, wh, ww, dtype) is served, else 0 with the reason set.  _rows: -1 if refused. */
+int htrvt_attn_win2d_supported(int hd, int wh, int ww, int dtype);
+int htrvt_attn_win2d_fwd(const void* qkv, const float* table, void* out, int B, int H, int W, int heads, int hd, int wh, int ww,
+                         int sh, int sw, float scale, int dtype, void* stream);
+int htrvt_attn_win2d_rows(int B, int H, int W, int heads, int wh, int ww);
+int htrvt_attn_win2d_bwd(const void* qkv, const float* table, const void* dout, void* dqkv, float* dtable_partial, int B, int H,
+                         int W, int heads, int hd, int wh, int ww, int sh, int sw, float scale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
