@@ -113,6 +113,12 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// every activation access is a 16-byte vector: true if one of the base pointers (null ones pass) is not 16-byte aligned
+template <typename... P>
+inline bool misaligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) != 0;
+}
+
 void set_error(const char* fmt, ...);
 void set_last_kernel(const char* fmt, ...);   // symbol (as rocprofv3 prints it) of the MFMA kernel an entry point launched
 int check_launch(const char* what);

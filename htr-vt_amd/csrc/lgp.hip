@@ -15,8 +15,9 @@
 //   htrvt_lgp_upsample_fwd/bwd   F.interpolate(mode="linear", align_corners=False) G -> N times sigmoid(logit_alpha) (:69-76),
 //                                written with a row stride (the right half of the fuse Linear's [B N][2D] operand).  Backward by
 //                                gather, d logit_alpha by a two-stage ordered sum.
+// The window attention is the 1-D side of window_attn_impl.h's form: that header's forward kernel over the source below.
 // No float atomics anywhere: every result is bitwise reproducible.
-#include "chunkmath.h"
+#include "window_attn_impl.h"
 
 using namespace htrvt;
 
@@ -25,146 +26,68 @@ namespace {
 constexpr int NT = 256;
 constexpr int WMAX = 16;          // largest window: one query row per group of four lanes
 
-// sum over the four lanes of a quad (lanes 4r .. 4r+3), result in all four
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-  return v;
-}
-
 // ------------------------------------------------------------------ window attention
-// One wave per (image, window, head).  Lane = (row r = lane / 4, part p = lane % 4): the lane owns the 16-byte chunks
-// c = 4 i + p of row r's head slice (any partition of the head dimension serves a dot product; this one makes four lanes
-// read 64 contiguous bytes).  k / v rows (and q / dO rows in the backward) are staged in LDS in their storage type, one
-// 16-byte chunk of padding per row so that the 16 rows of a store spread over all banks; reads of a row are broadcasts.
-template <typename T, int HD>
-struct LocalGeom {
-  using V = Vec16<T>;
-  using Raw = decltype(V().raw);
-  static constexpr int VN = V::N;          // elements per 16-byte chunk
-  static constexpr int CPR = HD / VN;      // chunks per row
-  static constexpr int CH = CPR / 4;       // chunks per lane
-  static constexpr int EPL = CH * VN;      // elements per lane
-  static constexpr int RS = CPR + 1;       // LDS row stride in chunks
-  static constexpr int MAT = WMAX * RS;    // chunks per staged matrix
-};
-
+// The 1-D source of window_attn_impl.h's form: four lanes per row, rows that are no token (the padding slots of a ragged last
+// window) built from the qkv bias, nothing added to a score.
 struct LocalUnit {
-  int b, head, r, p, tok, nvalid;
+  int b, head, n, nvalid;                  // n = w rows in the window, the first nvalid of them tokens
+  long long tok;                           // the token's row of qkv / out
   bool rowact, real;
 };
 
 // Shifted windows (WindowMHSA1D with shift s: roll the tokens by s, pad, attend, crop, roll back) are index arithmetic: token j
 // sits in rolled slot (j + s) mod N, window t holds slots [t w, t w + w), slots >= N of the last window are the padding rows,
 // and slot p < N reads and writes token (p - s) mod N.  `shift` arrives reduced mod N, so that is one compare and one add.
-__device__ __forceinline__ LocalUnit local_unit(long long u, long long units, int N, int heads, int w, int nW, int shift,
-                                                int lane) {
-  LocalUnit x;
-  const bool valid = u < units;
-  const long long uu = valid ? u : 0;
-  x.head = (int)(uu % heads);
-  const int win = (int)((uu / heads) % nW);
-  x.b = (int)(uu / ((long long)heads * nW));
-  x.r = lane >> 2;
-  x.p = lane & 3;
-  const int slot = win * w + x.r;
-  x.tok = slot - shift + (slot < shift ? N : 0);
-  const int left = N - win * w;            // real slots of this window
-  x.nvalid = left < w ? left : w;
-  x.rowact = valid && x.r < w;
-  x.real = x.rowact && x.r < x.nvalid;
-  return x;
-}
+struct Local1d {
+  static constexpr int LPR = 4;
+  static constexpr bool PADS = true;
+  const float* bias;
+  int N, heads, w, nW, shift;
 
-template <typename T, int HD, int WPB>
-__global__ __launch_bounds__(64 * WPB) void attn_local_fwd_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
-                                                                  T* __restrict__ out, int N, int heads, int w, int nW,
-                                                                  int shift, float scale, long long units) {
-  using G = LocalGeom<T, HD>;
-  using V = typename G::V;
-  using Raw = typename G::Raw;
-  __shared__ Raw lds[WPB][2][G::MAT];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, shift, lane);
-  const int D = heads * HD;
-  Raw* kl = lds[wv][0];
-  Raw* vl = lds[wv][1];
-  Raw q[G::CH];
-#pragma unroll
-  for (int i = 0; i < G::CH; ++i) q[i] = Raw{};
-  if (x.real) {
-    const Raw* src = reinterpret_cast<const Raw*>(qkv + ((long long)x.b * N + x.tok) * 3 * D + x.head * HD);
-#pragma unroll
-    for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 4 + x.p;
-      q[i] = src[c];
-      kl[x.r * G::RS + c] = src[D / G::VN + c];
-      vl[x.r * G::RS + c] = src[2 * D / G::VN + c];
-    }
-  } else if (x.rowact) {                   // padding slot: the row the qkv Linear makes of a zero token
-    const float* bk = bias + D + x.head * HD;
+  __device__ __forceinline__ LocalUnit unit(long long u, long long units, int r) const {
+    LocalUnit x;
+    const bool valid = u < units;
+    const long long uu = valid ? u : 0;
+    x.head = (int)(uu % heads);
+    const int win = (int)((uu / heads) % nW);
+    x.b = (int)(uu / ((long long)heads * nW));
+    const int slot = win * w + r;
+    x.tok = (long long)x.b * N + (slot - shift + (slot < shift ? N : 0));
+    const int left = N - win * w;          // real slots of this window
+    x.n = w;
+    x.nvalid = left < w ? left : w;
+    x.rowact = valid && r < w;
+    x.real = x.rowact && r < x.nvalid;
+    return x;
+  }
+  struct Lds {};
+  __device__ __forceinline__ void stage_extras(Lds*, const LocalUnit&, int) const {}
+  // padding slot: the k / v row the qkv Linear makes of a zero token
+  template <class G>
+  __device__ __forceinline__ void pad_row(typename G::Raw* kl, typename G::Raw* vl, const LocalUnit& x, int r, int part) const {
+    const int D = heads * G::CPR * G::VN;
+    const float* bk = bias + D + x.head * (G::CPR * G::VN);
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 4 + x.p;
-      V kk, vv;
+      const int c = i * 4 + part;
+      typename G::V kk, vv;
 #pragma unroll
       for (int e = 0; e < G::VN; ++e) {
         kk.set(e, bk[c * G::VN + e]);
         vv.set(e, bk[D + c * G::VN + e]);
       }
-      kl[x.r * G::RS + c] = kk.raw;
-      vl[x.r * G::RS + c] = vv.raw;
+      kl[r * G::RS + c] = kk.raw;
+      vl[r * G::RS + c] = vv.raw;
     }
   }
-  __syncthreads();
+  __device__ __forceinline__ PlainScore score(Lds*, const LocalUnit&) const { return PlainScore{}; }
+};
 
-  float s[WMAX];
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < WMAX; ++j) {
-    s[j] = -INFINITY;
-    if (j < w) {
-      float acc = 0.f;
-#pragma unroll
-      for (int i = 0; i < G::CH; ++i) acc = ChunkDot<T>::run(acc, q[i], kl[j * G::RS + i * 4 + x.p]);
-      s[j] = quad_sum(acc) * scale;
-      m = fmaxf(m, s[j]);
-    }
-  }
-  float o[G::EPL];
-#pragma unroll
-  for (int e = 0; e < G::EPL; ++e) o[e] = 0.f;
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < WMAX; j += 2) {
-    if (j < w) {
-      const bool two = j + 1 < w;          // an odd window's last row goes alone (its partner: the same row, weight 0)
-      const float p0 = __expf(s[j] - m), p1 = two ? __expf(s[j + 1] - m) : 0.f;
-      sum += p0 + p1;
-      const auto c = Axpy2<T>::coef(p0, p1);
-      const int j1 = two ? j + 1 : j;
-#pragma unroll
-      for (int i = 0; i < G::CH; ++i)
-        Axpy2<T>::run(&o[i * G::VN], c, vl[j * G::RS + i * 4 + x.p], vl[j1 * G::RS + i * 4 + x.p]);
-    }
-  }
-  if (x.real) {
-    const float inv = 1.0f / sum;
-    Raw* dst = reinterpret_cast<Raw*>(out + ((long long)x.b * N + x.tok) * D + x.head * HD);
-#pragma unroll
-    for (int i = 0; i < G::CH; ++i) {
-      V a;
-#pragma unroll
-      for (int e = 0; e < G::VN; ++e) a.set(e, o[i * G::VN + e] * inv);
-      dst[i * 4 + x.p] = a.raw;
-    }
-  }
-}
-
-// Backward.  Phase 1, lane (query r, p): P and dS of row r from the staged rows, left in LDS ([16][17] floats each).
-// Phase 2: dq[r] = sum_j dS[r][j] k[j]; then, the lane's row taken as key j: dk[j] = sum_r dS[r][j] q[r],
-// dv[j] = sum_r P[r][j] dO[r] over the staged q / dO rows.  The `pad` padding keys of a ragged
-// window are the same row, so each gets the same gradient: the first of them writes pad x its own into dpad.
+// Backward, one unit per wave and all four matrices (q, k, v, dO) staged at once.  Phase 1, lane (query r, p): P and dS of row
+// r (dS times the score scale), left in LDS.  Phase 2: dq[r] = sum_j dS[r][j] k[j]; then, the lane's row taken as key j:
+// dk[j] = sum_r dS[r][j] q[r], dv[j] = sum_r P[r][j] dO[r] over the staged q / dO rows.  The `pad` padding keys of a ragged
+// window are the same row, so each gets the same gradient: the first of them writes pad x its own into dpad.  (The phases
+// are swin.hip's too and stand in both kernels: window_attn_impl.h says why.)
 // (3 waves per SIMD asked for as a register cap of 168: the LDS budget limits occupancy to 1 or 2 anyway -- hence the silenced
 // "failed to meet occupancy target" --, and left alone the compiler hoists every staged row into registers, takes all 256
 // and schedules worse: measured 192 against 130 us.  The pragma spans this one definition; compiled without it the file
@@ -176,13 +99,14 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
                                                                   const T* __restrict__ dout, T* __restrict__ dqkv,
                                                                   float* __restrict__ dpad, int N, int heads, int w, int nW,
                                                                   int shift, float scale, long long units) {
-  using G = LocalGeom<T, HD>;
+  using G = WinAttnGeom<T, HD, 4>;
   using V = typename G::V;
   using Raw = typename G::Raw;
   __shared__ Raw lds[WPB][4][G::MAT];
   __shared__ float coef[WPB][2][WMAX][WMAX + 1];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const LocalUnit x = local_unit((long long)blockIdx.x * WPB + wv, units, N, heads, w, nW, shift, lane);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane >> 2, p = lane & 3;
+  const Local1d win{bias, N, heads, w, nW, shift};
+  const LocalUnit x = win.unit((long long)blockIdx.x * WPB + wv, units, r);
   const int D = heads * HD;
   Raw* ql = lds[wv][0];
   Raw* kl = lds[wv][1];
@@ -193,19 +117,18 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
   Raw q[G::CH], g[G::CH];
 #pragma unroll
   for (int i = 0; i < G::CH; ++i) q[i] = g[i] = Raw{};
-  const long long row = (long long)x.b * N + x.tok;
   if (x.real) {
-    const Raw* src = reinterpret_cast<const Raw*>(qkv + row * 3 * D + x.head * HD);
-    const Raw* gsrc = reinterpret_cast<const Raw*>(dout + row * D + x.head * HD);
+    const Raw* src = reinterpret_cast<const Raw*>(qkv + x.tok * 3 * D + x.head * HD);
+    const Raw* gsrc = reinterpret_cast<const Raw*>(dout + x.tok * D + x.head * HD);
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 4 + x.p;
+      const int c = i * 4 + p;
       q[i] = src[c];
       g[i] = gsrc[c];
-      ql[x.r * G::RS + c] = q[i];
-      gl[x.r * G::RS + c] = g[i];
-      kl[x.r * G::RS + c] = src[D / G::VN + c];
-      vl[x.r * G::RS + c] = src[2 * D / G::VN + c];
+      ql[r * G::RS + c] = q[i];
+      gl[r * G::RS + c] = g[i];
+      kl[r * G::RS + c] = src[D / G::VN + c];
+      vl[r * G::RS + c] = src[2 * D / G::VN + c];
     }
   } else if (x.rowact) {
     const float* bk = bias + D + x.head * HD;
@@ -214,17 +137,17 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
     for (int e = 0; e < G::VN; ++e) z.set(e, 0.f);
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 4 + x.p;
+      const int c = i * 4 + p;
       V kk, vv;
 #pragma unroll
       for (int e = 0; e < G::VN; ++e) {
         kk.set(e, bk[c * G::VN + e]);
         vv.set(e, bk[D + c * G::VN + e]);
       }
-      kl[x.r * G::RS + c] = kk.raw;
-      vl[x.r * G::RS + c] = vv.raw;
-      ql[x.r * G::RS + c] = z.raw;         // a padded query's output is cropped: it sends no gradient
-      gl[x.r * G::RS + c] = z.raw;
+      kl[r * G::RS + c] = kk.raw;
+      vl[r * G::RS + c] = vv.raw;
+      ql[r * G::RS + c] = z.raw;         // a padded query's output is cropped: it sends no gradient
+      gl[r * G::RS + c] = z.raw;
     }
   }
   __syncthreads();
@@ -239,11 +162,11 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
       float acc = 0.f, accv = 0.f;
 #pragma unroll
       for (int i = 0; i < G::CH; ++i) {
-        acc = ChunkDot<T>::run(acc, q[i], kl[j * G::RS + i * 4 + x.p]);
-        accv = ChunkDot<T>::run(accv, g[i], vl[j * G::RS + i * 4 + x.p]);
+        acc = ChunkDot<T>::run(acc, q[i], kl[j * G::RS + i * 4 + p]);
+        accv = ChunkDot<T>::run(accv, g[i], vl[j * G::RS + i * 4 + p]);
       }
-      s[j] = quad_sum(acc) * scale;
-      dp[j] = quad_sum(accv);
+      s[j] = row_sum<4>(acc) * scale;
+      dp[j] = row_sum<4>(accv);
       m = fmaxf(m, s[j]);
     }
   }
@@ -269,9 +192,9 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
   for (int j = 0; j < WMAX; ++j) {
     if (j < w) {
       dp[j] = s[j] * (dp[j] - delta) * scale;      // dS
-      if (x.p == 0 && x.r < w) {
-        Pl[x.r][j] = s[j];
-        Sl[x.r][j] = dp[j];
+      if (p == 0 && r < w) {
+        Pl[r][j] = s[j];
+        Sl[r][j] = dp[j];
       }
     }
   }
@@ -279,7 +202,7 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
 
   // dq of this lane's query row.  The coefficients come back from LDS, not from the register arrays above, so that the row
   // loops here need no full unrolling (fully unrolled they took every VGPR and ran slower)
-  const int jr = x.r < w ? x.r : 0;
+  const int jr = r < w ? r : 0;
 #pragma unroll 2
   for (int j = 0; j < w; j += 2) {
     const bool two = j + 1 < w;
@@ -287,33 +210,33 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
     const auto c = Axpy2<T>::coef(Sl[jr][j], two ? Sl[jr][j1] : 0.f);
 #pragma unroll
     for (int i = 0; i < G::CH; ++i)
-      Axpy2<T>::run(&dq[i * G::VN], c, kl[j * G::RS + i * 4 + x.p], kl[j1 * G::RS + i * 4 + x.p]);
+      Axpy2<T>::run(&dq[i * G::VN], c, kl[j * G::RS + i * 4 + p], kl[j1 * G::RS + i * 4 + p]);
   }
-  Raw* drow = reinterpret_cast<Raw*>(dqkv + row * 3 * D + x.head * HD);
+  Raw* drow = reinterpret_cast<Raw*>(dqkv + x.tok * 3 * D + x.head * HD);
   if (x.real) {
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
       V a;
 #pragma unroll
       for (int e = 0; e < G::VN; ++e) a.set(e, dq[i * G::VN + e]);
-      drow[i * 4 + x.p] = a.raw;
+      drow[i * 4 + p] = a.raw;
     }
   }
 
-  // phase 2: this lane's row is now key / value row j = x.r
+  // phase 2: this lane's row is now key / value row j = r
   float dk[G::EPL], dv[G::EPL];
 #pragma unroll
   for (int e = 0; e < G::EPL; ++e) dk[e] = dv[e] = 0.f;
 #pragma unroll 2
-  for (int r = 0; r < w; r += 2) {
-    const bool two = r + 1 < w;
-    const int r1 = two ? r + 1 : r;
-    const auto cs = Axpy2<T>::coef(Sl[r][jr], two ? Sl[r1][jr] : 0.f);
-    const auto cp = Axpy2<T>::coef(Pl[r][jr], two ? Pl[r1][jr] : 0.f);
+  for (int i0 = 0; i0 < w; i0 += 2) {          // query rows i0, i1
+    const bool two = i0 + 1 < w;
+    const int i1 = two ? i0 + 1 : i0;
+    const auto cs = Axpy2<T>::coef(Sl[i0][jr], two ? Sl[i1][jr] : 0.f);
+    const auto cp = Axpy2<T>::coef(Pl[i0][jr], two ? Pl[i1][jr] : 0.f);
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
-      Axpy2<T>::run(&dk[i * G::VN], cs, ql[r * G::RS + i * 4 + x.p], ql[r1 * G::RS + i * 4 + x.p]);
-      Axpy2<T>::run(&dv[i * G::VN], cp, gl[r * G::RS + i * 4 + x.p], gl[r1 * G::RS + i * 4 + x.p]);
+      Axpy2<T>::run(&dk[i * G::VN], cs, ql[i0 * G::RS + i * 4 + p], ql[i1 * G::RS + i * 4 + p]);
+      Axpy2<T>::run(&dv[i * G::VN], cp, gl[i0 * G::RS + i * 4 + p], gl[i1 * G::RS + i * 4 + p]);
     }
   }
   if (x.real) {
@@ -325,15 +248,15 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
         a.set(e, dk[i * G::VN + e]);
         d.set(e, dv[i * G::VN + e]);
       }
-      drow[D / G::VN + i * 4 + x.p] = a.raw;
-      drow[2 * D / G::VN + i * 4 + x.p] = d.raw;
+      drow[D / G::VN + i * 4 + p] = a.raw;
+      drow[2 * D / G::VN + i * 4 + p] = d.raw;
     }
-  } else if (x.rowact && x.r == x.nvalid) {      // first padding key of the image's ragged window
+  } else if (x.rowact && r == x.nvalid) {        // first padding key of the image's ragged window
     const float npad = (float)(w - x.nvalid);
     float* dst = dpad + (long long)x.b * 2 * D + x.head * HD;
 #pragma unroll
     for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 4 + x.p;
+      const int c = i * 4 + p;
 #pragma unroll
       for (int e = 0; e < G::VN; ++e) {
         dst[c * G::VN + e] = npad * dk[i * G::VN + e];
@@ -345,11 +268,9 @@ __global__ __launch_bounds__(64 * WPB, 3) void attn_local_bwd_kernel(const T* __
 
 #pragma clang diagnostic pop
 
-// every activation access is a 16-byte vector: true if one of the (up to four) base pointers is not 16-byte aligned
-inline bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<unsigned long long>(a) | reinterpret_cast<unsigned long long>(b) |
-           reinterpret_cast<unsigned long long>(c) | reinterpret_cast<unsigned long long>(d)) & 15) != 0;
-}
+// (dtype, hd) served and the waves per workgroup there: what the staged rows leave of the 64 KB of static LDS
+#define ATTN_LOCAL_FWD_WPB(X) X(bf16_t, 128, 4) X(bf16_t, 64, 4) X(float, 128, 2) X(float, 64, 4)
+#define ATTN_LOCAL_BWD_WPB(X) X(bf16_t, 128, 2) X(bf16_t, 64, 4) X(float, 128, 1) X(float, 64, 2)
 
 int local_check(const char* who, int B, int N, int heads, int hd, int w, int dtype) {
   HTRVT_REQUIRE(dtype == HTRVT_F32 || dtype == HTRVT_BF16, "%s: dtype %d (float32 or bfloat16)", who, dtype);
@@ -626,9 +547,6 @@ extern "C" int htrvt_attn_local_shift_supported(int hd, int window, int shift, i
   return shift_check("htrvt_attn_local_shift", window, shift) == 0 ? 1 : 0;
 }
 
-#define LOCAL_LAUNCH(KERNEL, T, HD, WPB, ...)                                                                   \
-  hipLaunchKernelGGL((KERNEL<T, HD, WPB>), dim3((unsigned)((units + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, __VA_ARGS__)
-
 // the two entry points of each direction share one launch; `shift` is checked by the caller and reduced mod N here
 static int local_fwd(const char* who, const void* qkv, const float* qkv_bias, void* out, int B, int N, int heads, int hd,
                      int window, int shift, float scale, int dtype, void* stream) {
@@ -641,17 +559,11 @@ static int local_fwd(const char* who, const void* qkv, const float* qkv_bias, vo
   HTRVT_REQUIRE(units < (1ll << 31), "%s: too many windows", who);
   hipStream_t st = (hipStream_t)stream;
   const int sh = shift % N;
-  if (dtype == HTRVT_BF16) {
-    if (hd == 128)
-      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 128, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, sh, scale, units);
-    else
-      LOCAL_LAUNCH(attn_local_fwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (bf16_t*)out, N, heads, window, nW, sh, scale, units);
-  } else {
-    if (hd == 128)
-      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 128, 2, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, sh, scale, units);
-    else
-      LOCAL_LAUNCH(attn_local_fwd_kernel, float, 64, 4, (const float*)qkv, qkv_bias, (float*)out, N, heads, window, nW, sh, scale, units);
-  }
+#define WINDOW_ATTN_LAUNCH(T, HD, WPB)                                                                                    \
+  hipLaunchKernelGGL((window_attn_fwd_kernel<T, HD, WPB, Local1d>), dim3((unsigned)((units + WPB - 1) / WPB)), dim3(64 * WPB), 0, \
+                     st, Local1d{qkv_bias, N, heads, window, nW, sh}, (const T*)qkv, (T*)out, scale, units)
+  ATTN_LOCAL_FWD_WPB(WINDOW_ATTN_ROW)
+#undef WINDOW_ATTN_LAUNCH
   return check_launch("attn_local_fwd");
 }
 
@@ -669,17 +581,11 @@ static int local_bwd(const char* who, const void* qkv, const float* qkv_bias, co
     HTRVT_REQUIRE(hipMemsetAsync(dpad, 0, sizeof(float) * 2 * (size_t)B * heads * hd, st) == hipSuccess,
                   "%s: clearing dpad failed", who);
   const int sh = shift % N;
-  if (dtype == HTRVT_BF16) {
-    if (hd == 128)
-      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 128, 2, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
-    else
-      LOCAL_LAUNCH(attn_local_bwd_kernel, bf16_t, 64, 4, (const bf16_t*)qkv, qkv_bias, (const bf16_t*)dout, (bf16_t*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
-  } else {
-    if (hd == 128)
-      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 128, 1, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
-    else
-      LOCAL_LAUNCH(attn_local_bwd_kernel, float, 64, 2, (const float*)qkv, qkv_bias, (const float*)dout, (float*)dqkv, dpad, N, heads, window, nW, sh, scale, units);
-  }
+#define WINDOW_ATTN_LAUNCH(T, HD, WPB)                                                                                    \
+  hipLaunchKernelGGL((attn_local_bwd_kernel<T, HD, WPB>), dim3((unsigned)((units + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, \
+                     (const T*)qkv, qkv_bias, (const T*)dout, (T*)dqkv, dpad, N, heads, window, nW, sh, scale, units)
+  ATTN_LOCAL_BWD_WPB(WINDOW_ATTN_ROW)
+#undef WINDOW_ATTN_LAUNCH
   return check_launch("attn_local_bwd");
 }
 

@@ -372,8 +372,6 @@ __global__ __launch_bounds__(NT) void mixer_bwd_kernel(const T* __restrict__ u, 
 }
 
 // ------------------------------------------------------------------ host side
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_shape(const char* what, int B, int N, int D, int k, int dtype) {
   HTRVT_REQUIRE(dtype == HTRVT_F32 || dtype == HTRVT_BF16, "%s: dtype %d", what, dtype);
   HTRVT_REQUIRE(B >= 1 && N >= 1 && D >= 8, "%s: B=%d N=%d D=%d", what, B, N, D);
@@ -455,7 +453,7 @@ extern "C" int htrvt_mixer_fwd_train(const void* u, const float* w, void* c, flo
   if (check_shape("htrvt_mixer_fwd_train", B, N, D, k, dtype)) return -1;
   HTRVT_REQUIRE((long long)B * N >= 2, "htrvt_mixer_fwd_train: batch statistics need B * N >= 2 values per channel");
   HTRVT_REQUIRE(u && w && c && partial, "htrvt_mixer_fwd_train: null buffer");
-  HTRVT_REQUIRE(aligned16(u) && aligned16(c), "htrvt_mixer_fwd_train: u / c not 16-byte aligned");
+  HTRVT_REQUIRE(!misaligned16(u, c), "htrvt_mixer_fwd_train: u / c not 16-byte aligned");
   Split sp;
   HTRVT_REQUIRE(make_split(B, N, D, dtype, &sp), "htrvt_mixer_fwd_train: B=%d N=%d does not fit one launch", B, N);
   if (dtype == HTRVT_BF16)
@@ -471,7 +469,7 @@ extern "C" int htrvt_mixer_bn_silu(const void* c, const float* scale, const floa
   HTRVT_REQUIRE(rows >= 0 && D >= 8 && D % 8 == 0, "htrvt_mixer_bn_silu: rows=%lld, D=%d (a multiple of 8)", (long long)rows, D);
   if (rows == 0) return 0;
   HTRVT_REQUIRE(c && s, "htrvt_mixer_bn_silu: null buffer");
-  HTRVT_REQUIRE(aligned16(c) && aligned16(s), "htrvt_mixer_bn_silu: c / s not 16-byte aligned");
+  HTRVT_REQUIRE(!misaligned16(c, s), "htrvt_mixer_bn_silu: c / s not 16-byte aligned");
   const int dv = D / (dtype == HTRVT_BF16 ? 8 : 4);
   int lcw = 0;
   while ((1 << lcw) < dv && lcw < 5) ++lcw;
@@ -490,7 +488,7 @@ extern "C" int htrvt_mixer_fwd_eval(const void* u, const float* w, const float* 
                                     int B, int N, int D, int k, int dtype, void* stream) {
   if (check_shape("htrvt_mixer_fwd_eval", B, N, D, k, dtype)) return -1;
   HTRVT_REQUIRE(u && w && s, "htrvt_mixer_fwd_eval: null buffer");
-  HTRVT_REQUIRE(aligned16(u) && aligned16(c) && aligned16(s), "htrvt_mixer_fwd_eval: u / c / s not 16-byte aligned");
+  HTRVT_REQUIRE(!misaligned16(u, c, s), "htrvt_mixer_fwd_eval: u / c / s not 16-byte aligned");
   Split sp;
   HTRVT_REQUIRE(make_split(B, N, D, dtype, &sp), "htrvt_mixer_fwd_eval: B=%d N=%d does not fit one launch", B, N);
   if (dtype == HTRVT_BF16)
@@ -505,7 +503,7 @@ extern "C" int htrvt_mixer_bwd_reduce(const void* ds, const void* c, const float
   HTRVT_REQUIRE(dtype == HTRVT_F32 || dtype == HTRVT_BF16, "htrvt_mixer_bwd_reduce: dtype %d", dtype);
   HTRVT_REQUIRE(rows >= 1 && D >= 8 && D % 8 == 0, "htrvt_mixer_bwd_reduce: rows=%lld, D=%d (a multiple of 8)", (long long)rows, D);
   HTRVT_REQUIRE(ds && c && partial && (!mean || rstd), "htrvt_mixer_bwd_reduce: null buffer");
-  HTRVT_REQUIRE(aligned16(ds) && aligned16(c), "htrvt_mixer_bwd_reduce: ds / c not 16-byte aligned");
+  HTRVT_REQUIRE(!misaligned16(ds, c), "htrvt_mixer_bwd_reduce: ds / c not 16-byte aligned");
   const int dv = D / (dtype == HTRVT_BF16 ? 8 : 4);
   int lcw = 0;
   while ((1 << lcw) < dv && lcw < 5) ++lcw;
@@ -524,7 +522,7 @@ extern "C" int htrvt_mixer_bwd(const void* u, const void* c, const void* ds, con
                                int N, int D, int k, int dtype, void* stream) {
   if (check_shape("htrvt_mixer_bwd", B, N, D, k, dtype)) return -1;
   HTRVT_REQUIRE(u && c && ds && w && du && dw_partial, "htrvt_mixer_bwd: null buffer");
-  HTRVT_REQUIRE(aligned16(u) && aligned16(c) && aligned16(ds) && aligned16(du), "htrvt_mixer_bwd: u / c / ds / du not 16-byte aligned");
+  HTRVT_REQUIRE(!misaligned16(u, c, ds, du), "htrvt_mixer_bwd: u / c / ds / du not 16-byte aligned");
   Split sp;
   HTRVT_REQUIRE(make_split(B, N, D, dtype, &sp), "htrvt_mixer_bwd: B=%d N=%d does not fit one launch", B, N);
   if (dtype == HTRVT_BF16)

@@ -8,11 +8,13 @@
 //                              the chip and nothing but qkv is saved: the backward recomputes the (at most 32 x 32) softmax.
 //                              The table gradient leaves as partial rows for htrvt_rowsum_f32, one per share of the
 //                              (image, window) items, each an ordered sum.
-// The scores stay on the VALU, in the form of lgp.hip's window kernels: a 32-token window of a 32-wide head is 2 x 32 x 32 x 32
-// multiply-adds per product, the launch is bound by HBM traffic and load latency, and an MFMA tile would have to get the
-// bias, the mask and the softmax out of the accumulator layout for no gain in the bound.
+// The scores stay on the VALU, in the form of window_attn_impl.h that lgp.hip's 1-D windows share: a 32-token window of a
+// 32-wide head is 2 x 32 x 32 x 32 multiply-adds per product, the launch is bound by HBM traffic and load latency, and an MFMA
+// tile would have to get the bias, the mask and the softmax out of the accumulator layout for no gain in the bound.
+// This file holds what is the 2-D windows' own: the window source of the header's forward kernel (slot-to-token map, table
+// entry and mask added to a score) and the backward kernel with its walk over a share's items and the table-gradient gather.
 // No float atomics anywhere: every result is bitwise reproducible.
-#include "chunkmath.h"
+#include "window_attn_impl.h"
 
 using namespace htrvt;
 
@@ -20,27 +22,6 @@ namespace {
 
 constexpr int NMAX = 32;          // largest window: one query row per pair of lanes
 constexpr int TMAX = 128;         // table entries per head: (2wh-1)(2ww-1) <= 105 when wh ww <= 32
-
-// sum over the two lanes of a pair (lanes 2r, 2r+1), result in both
-__device__ __forceinline__ float pair_sum(float v) {
-  return v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-}
-
-// One wave per (image, window, head).  Lane = (slot t = lane / 2, part p = lane % 2): the lane owns the 16-byte chunks
-// c = 2 i + p of slot t's head slice.  k / v rows (q / dO rows in the backward's second phase) are staged in LDS in their
-// storage type, one 16-byte chunk of padding per row so that the rows of a store spread over the banks; reads of a row are
-// broadcasts.
-template <typename T, int HD>
-struct WinGeom {
-  using V = Vec16<T>;
-  using Raw = decltype(V().raw);
-  static constexpr int VN = V::N;          // elements per 16-byte chunk
-  static constexpr int CPR = HD / VN;      // chunks per row
-  static constexpr int CH = CPR / 2;       // chunks per lane
-  static constexpr int EPL = CH * VN;      // elements per lane
-  static constexpr int RS = CPR + 1;       // LDS row stride in chunks
-  static constexpr int MAT = NMAX * RS;    // chunks per staged matrix
-};
 
 struct Win2d {
   int H, W, heads, wh, ww, sh, sw, nWw, nWin;   // nWw windows across, nWin = (H / wh) nWw windows per image
@@ -75,101 +56,66 @@ __device__ __forceinline__ int query_base(const Win2d& g, const Slot& x) {
   return (x.r + g.wh - 1) * (2 * g.ww - 1) + x.c + g.ww - 1;
 }
 
-template <typename T, int HD, int WPB>
-__global__ __launch_bounds__(64 * WPB) void win2d_fwd_kernel(const T* __restrict__ qkv, const float* __restrict__ table,
-                                                             T* __restrict__ out, Win2d g, long long units) {
-  using G = WinGeom<T, HD>;
-  using V = typename G::V;
-  using Raw = typename G::Raw;
-  __shared__ Raw lds[WPB][2][G::MAT];
-  __shared__ float tbl[WPB][TMAX];
-  __shared__ int key[WPB][NMAX];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const long long u = (long long)blockIdx.x * WPB + wv;
-  const bool valid = u < units;
-  const long long uu = valid ? u : 0;
-  const int head = (int)(uu % g.heads);
-  const int n = g.wh * g.ww, t = lane >> 1, p = lane & 1;
-  const Slot x = win_slot(g, uu / g.heads, t < n ? t : 0);
-  const bool act = valid && t < n;
-  const int D = g.heads * HD, TE = (2 * g.wh - 1) * (2 * g.ww - 1);
-  Raw* kl = lds[wv][0];
-  Raw* vl = lds[wv][1];
-  for (int e = lane; e < TE; e += 64) tbl[wv][e] = table[(long long)e * g.heads + head];
-  if (p == 0 && t < n) key[wv][t] = key_code(g, x);
-  Raw q[G::CH];
-#pragma unroll
-  for (int i = 0; i < G::CH; ++i) q[i] = Raw{};
-  if (act) {
-    const Raw* src = reinterpret_cast<const Raw*>(qkv + x.tok * 3 * D + head * HD);
-#pragma unroll
-    for (int i = 0; i < G::CH; ++i) {
-      const int c = i * 2 + p;
-      q[i] = src[c];
-      kl[t * G::RS + c] = src[D / G::VN + c];
-      vl[t * G::RS + c] = src[2 * D / G::VN + c];
-    }
+// score of (query x, key row j) = scale q.k + the pair's table entry - 100 across mask regions; `tbl` is the head's column of
+// the table and `key` the key codes of the window's slots, both in LDS
+struct Win2dScore {
+  const float* tbl;
+  const int* key;
+  int base, reg;
+  __device__ __forceinline__ float operator()(float qk, int j) const {
+    const int kc = key[j];
+    return qk + tbl[base - (kc & 255)] + ((kc >> 8) != reg ? -100.0f : 0.f);
   }
-  __syncthreads();
+};
 
-  const int base = query_base(g, x);
-  float s[NMAX];
-  float m = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < NMAX; ++j) {
-    s[j] = -INFINITY;
-    if (j < n) {
-      float acc = 0.f;
-#pragma unroll
-      for (int i = 0; i < G::CH; ++i) acc = ChunkDot<T>::run(acc, q[i], kl[j * G::RS + i * 2 + p]);
-      const int kc = key[wv][j];
-      s[j] = pair_sum(acc) * g.scale + tbl[wv][base - (kc & 255)] + ((kc >> 8) != x.reg ? -100.0f : 0.f);
-      m = fmaxf(m, s[j]);
-    }
+struct Unit2d : Slot {
+  int head, n;
+  bool rowact, real;
+};
+
+// The 2-D source of the form: two lanes per row, every row of a window a token
+struct Win2dSource : Win2d {
+  static constexpr int LPR = 2;
+  static constexpr bool PADS = false;
+  struct Lds {
+    float tbl[TMAX];
+    int key[NMAX];
+  };
+  const float* table;
+
+  __device__ __forceinline__ Unit2d unit(long long u, long long units, int t) const {
+    const bool valid = u < units;
+    const long long uu = valid ? u : 0;
+    Unit2d x;
+    x.n = wh * ww;
+    static_cast<Slot&>(x) = win_slot(*this, uu / heads, t < x.n ? t : 0);
+    x.head = (int)(uu % heads);
+    x.rowact = x.real = valid && t < x.n;
+    return x;
   }
-  float o[G::EPL];
-#pragma unroll
-  for (int e = 0; e < G::EPL; ++e) o[e] = 0.f;
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < NMAX; j += 2) {
-    if (j < n) {
-      const bool two = j + 1 < n;          // an odd window's last row goes alone (its partner: the same row, weight 0)
-      const float p0 = __expf(s[j] - m), p1 = two ? __expf(s[j + 1] - m) : 0.f;
-      sum += p0 + p1;
-      const auto c = Axpy2<T>::coef(p0, p1);
-      const int j1 = two ? j + 1 : j;
-#pragma unroll
-      for (int i = 0; i < G::CH; ++i)
-        Axpy2<T>::run(&o[i * G::VN], c, vl[j * G::RS + i * 2 + p], vl[j1 * G::RS + i * 2 + p]);
-    }
+  __device__ __forceinline__ void stage_extras(Lds* ext, const Unit2d& x, int lane) const {
+    const int TE = (2 * wh - 1) * (2 * ww - 1);
+    for (int e = lane; e < TE; e += 64) ext->tbl[e] = table[(long long)e * heads + x.head];
+    if ((lane & 1) == 0 && (lane >> 1) < x.n) ext->key[lane >> 1] = key_code(*this, x);
   }
-  if (act) {
-    const float inv = 1.0f / sum;
-    Raw* dst = reinterpret_cast<Raw*>(out + x.tok * D + head * HD);
-#pragma unroll
-    for (int i = 0; i < G::CH; ++i) {
-      V a;
-#pragma unroll
-      for (int e = 0; e < G::VN; ++e) a.set(e, o[i * G::VN + e] * inv);
-      dst[i * 2 + p] = a.raw;
-    }
+  __device__ __forceinline__ Win2dScore score(const Lds* ext, const Unit2d& x) const {
+    return Win2dScore{ext->tbl, ext->key, query_base(*this, x), x.reg};
   }
-}
+};
 
 // Backward.  Workgroup (head, share): its WPB waves walk the (image, window) items of partial row `share`, one item per wave
 // and step, every wave the same number of steps.  Per item: phase 1, lane (query t, p): P and dS of row t from the staged k / v
-// rows, left in LDS ([32][33] floats each; dS without the score scale, which is the table's gradient).  Then dq[t] =
-// scale sum_j dS[t][j] k[j], and the wave's share of the table gradient: lane l gathers entries l and l + 64 from dS in key
-// order.  Phase 2 restages q / dO over k / v, and the lane's slot taken as key j: dk[j] = scale sum_r dS[r][j] q[r],
-// dv[j] = sum_r P[r][j] dO[r].  After the walk the waves' table sums are added in wave order into the partial row.
+// rows, left in LDS (dS without the score scale, which is the table's gradient).  Then dq[t] = scale sum_j dS[t][j] k[j], and
+// the wave's share of the table gradient: lane l gathers entries l and l + 64 from dS in key order.  Phase 2 restages q / dO
+// over k / v, and the lane's slot taken as key j: dk[j] = scale sum_r dS[r][j] q[r], dv[j] = sum_r P[r][j] dO[r].  After the
+// walk the waves' table sums are added in wave order into the partial row.
 // (The rows of phase 2 overwrite those of phase 1 so that a float32 head of 128 fits the 64 KB of static LDS.  As in lgp.hip's
 // backward the coefficients come back from LDS and the row loops are not fully unrolled.)
 template <typename T, int HD, int WPB>
 __global__ __launch_bounds__(64 * WPB) void win2d_bwd_kernel(const T* __restrict__ qkv, const float* __restrict__ table,
                                                              const T* __restrict__ dout, T* __restrict__ dqkv,
                                                              float* __restrict__ partial, Win2d g, long long items, int rows) {
-  using G = WinGeom<T, HD>;
+  using G = WinAttnGeom<T, HD, 2>;
   using V = typename G::V;
   using Raw = typename G::Raw;
   __shared__ Raw lds[WPB][2][G::MAT];
@@ -239,8 +185,8 @@ __global__ __launch_bounds__(64 * WPB) void win2d_bwd_kernel(const T* __restrict
           accv = ChunkDot<T>::run(accv, go[i], vl[j * G::RS + i * 2 + p]);
         }
         const int kc = key[wv][j];
-        s[j] = pair_sum(acc) * g.scale + tbl[base - (kc & 255)] + ((kc >> 8) != x.reg ? -100.0f : 0.f);
-        dp[j] = pair_sum(accv);
+        s[j] = row_sum<2>(acc) * g.scale + tbl[base - (kc & 255)] + ((kc >> 8) != x.reg ? -100.0f : 0.f);
+        dp[j] = row_sum<2>(accv);
         m = fmaxf(m, s[j]);
       }
     }
@@ -355,11 +301,9 @@ __global__ __launch_bounds__(64 * WPB) void win2d_bwd_kernel(const T* __restrict
   }
 }
 
-// every activation access is a 16-byte vector: true if one of the base pointers is not 16-byte aligned
-inline bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((reinterpret_cast<unsigned long long>(a) | reinterpret_cast<unsigned long long>(b) |
-           reinterpret_cast<unsigned long long>(c)) & 15) != 0;
-}
+// (dtype, hd) served and the waves per workgroup there, forward and backward: what the staged rows leave of the 64 KB of
+// static LDS
+#define WIN2D_WPB(X) X(bf16_t, 128, 2) X(bf16_t, 64, 2) X(bf16_t, 32, 4) X(float, 128, 1) X(float, 64, 2) X(float, 32, 2)
 
 int kind_check(const char* who, int hd, int wh, int ww, int dtype) {
   HTRVT_REQUIRE(dtype == HTRVT_F32 || dtype == HTRVT_BF16, "%s: dtype %d (float32 or bfloat16)", who, dtype);
@@ -401,18 +345,6 @@ extern "C" int htrvt_attn_win2d_rows(int B, int H, int W, int heads, int wh, int
   return win2d_rows(win2d_items(B, H, W, wh, ww));
 }
 
-// waves per workgroup: what the staged rows leave of the 64 KB of static LDS
-#define WIN2D_DISPATCH(LAUNCH)                       \
-  if (dtype == HTRVT_BF16) {                         \
-    if (hd == 128) LAUNCH(bf16_t, 128, 2);           \
-    else if (hd == 64) LAUNCH(bf16_t, 64, 2);        \
-    else LAUNCH(bf16_t, 32, 4);                      \
-  } else {                                           \
-    if (hd == 128) LAUNCH(float, 128, 1);            \
-    else if (hd == 64) LAUNCH(float, 64, 2);         \
-    else LAUNCH(float, 32, 2);                       \
-  }
-
 extern "C" int htrvt_attn_win2d_fwd(const void* qkv, const float* table, void* out, int B, int H, int W, int heads, int hd,
                                     int wh, int ww, int sh, int sw, float scale, int dtype, void* stream) {
   const char* who = "htrvt_attn_win2d_fwd";
@@ -424,11 +356,11 @@ extern "C" int htrvt_attn_win2d_fwd(const void* qkv, const float* table, void* o
   HTRVT_REQUIRE(units < (1ll << 31), "%s: too many windows", who);
   const Win2d g = win2d_geom(H, W, heads, wh, ww, sh, sw, scale);
   hipStream_t st = (hipStream_t)stream;
-#define WIN2D_FWD(T, HD, WPB)                                                                                       \
-  hipLaunchKernelGGL((win2d_fwd_kernel<T, HD, WPB>), dim3((unsigned)((units + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, \
-                     (const T*)qkv, table, (T*)out, g, units)
-  WIN2D_DISPATCH(WIN2D_FWD)
-#undef WIN2D_FWD
+#define WINDOW_ATTN_LAUNCH(T, HD, WPB)                                                                              \
+  hipLaunchKernelGGL((window_attn_fwd_kernel<T, HD, WPB, Win2dSource>), dim3((unsigned)((units + WPB - 1) / WPB)), \
+                     dim3(64 * WPB), 0, st, Win2dSource{g, table}, (const T*)qkv, (T*)out, scale, units)
+  WIN2D_WPB(WINDOW_ATTN_ROW)
+#undef WINDOW_ATTN_LAUNCH
   return check_launch("attn_win2d_fwd");
 }
 
@@ -449,10 +381,10 @@ extern "C" int htrvt_attn_win2d_bwd(const void* qkv, const float* table, const v
   }
   HTRVT_REQUIRE(items * heads < (1ll << 31), "%s: too many windows", who);
   const Win2d g = win2d_geom(H, W, heads, wh, ww, sh, sw, scale);
-#define WIN2D_BWD(T, HD, WPB)                                                                                      \
+#define WINDOW_ATTN_LAUNCH(T, HD, WPB)                                                                             \
   hipLaunchKernelGGL((win2d_bwd_kernel<T, HD, WPB>), dim3(heads, rows), dim3(64 * WPB), 0, st, (const T*)qkv, table, \
                      (const T*)dout, (T*)dqkv, dtable_partial, g, items, rows)
-  WIN2D_DISPATCH(WIN2D_BWD)
-#undef WIN2D_BWD
+  WIN2D_WPB(WINDOW_ATTN_ROW)
+#undef WINDOW_ATTN_LAUNCH
   return check_launch("attn_win2d_bwd");
 }

@@ -325,8 +325,6 @@ __global__ __launch_bounds__(NT) void hpool_kernel(const T* __restrict__ in, T* 
 }
 
 // ------------------------------------------------------------------ host side
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_conv(const char* what, int B, int H, int W, int C, int kh, int kw, int dil, int dtype) {
   HTRVT_REQUIRE(dtype == HTRVT_F32 || dtype == HTRVT_BF16, "%s: dtype %d", what, dtype);
   HTRVT_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 8, "%s: B=%d H=%d W=%d C=%d", what, B, H, W, C);
@@ -370,7 +368,7 @@ int conv_entry(const char* what, const void* x, const float* w, const void* add,
                int kw, int dil, int flip, int dtype, void* stream) {
   if (check_conv(what, B, H, W, C, kh, kw, dil, dtype)) return -1;
   HTRVT_REQUIRE(x && w && y, "%s: null buffer", what);
-  HTRVT_REQUIRE(aligned16(x) && aligned16(y) && aligned16(add), "%s: a tensor is not 16-byte aligned", what);
+  HTRVT_REQUIRE(!misaligned16(x, y, add), "%s: a tensor is not 16-byte aligned", what);
   if (dtype == HTRVT_BF16)
     launch_conv<bf16_t>((hipStream_t)stream, x, w, add, y, B, H, W, C, kh, kw, dil, flip, dtype);
   else
@@ -408,8 +406,7 @@ template <int MODE>
 int ew_entry(const char* what, const void* a, const void* b, const void* c, const float* scale, const float* shift, void* o1,
              void* o2, long long rows, int C, int dtype, void* stream) {
   if (check_rows(what, rows, C, dtype)) return -1;
-  HTRVT_REQUIRE(aligned16(a) && aligned16(b) && aligned16(c) && aligned16(o1) && aligned16(o2),
-                "%s: a tensor is not 16-byte aligned", what);
+  HTRVT_REQUIRE(!misaligned16(a, b, c, o1, o2), "%s: a tensor is not 16-byte aligned", what);
   const RowGrid g = row_grid(rows, C, dtype, 4, 16384);
   if (dtype == HTRVT_BF16)
     hipLaunchKernelGGL((ew_kernel<bf16_t, MODE>), g.grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b,
@@ -427,7 +424,7 @@ int hpool_entry(const char* what, const void* in, void* out, int B, int H, int W
   const long long rows = (long long)B * W;
   if (check_rows(what, rows, C, dtype)) return -1;
   HTRVT_REQUIRE(in && out, "%s: null buffer", what);
-  HTRVT_REQUIRE(aligned16(in) && aligned16(out), "%s: a tensor is not 16-byte aligned", what);
+  HTRVT_REQUIRE(!misaligned16(in, out), "%s: a tensor is not 16-byte aligned", what);
   const RowGrid g = row_grid(rows, C, dtype, 1, 16384);
   if (dtype == HTRVT_BF16)
     hipLaunchKernelGGL((hpool_kernel<bf16_t, FWD>), g.grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)in, (bf16_t*)out,
@@ -465,7 +462,7 @@ extern "C" int htrvt_van_dw_bwd_weight(const void* x, const void* dy, float* par
   const char* what = "htrvt_van_dw_bwd_weight";
   if (check_conv(what, B, H, W, C, kh, kw, dil, dtype)) return -1;
   HTRVT_REQUIRE(x && dy && partial, "%s: null buffer", what);
-  HTRVT_REQUIRE(aligned16(x) && aligned16(dy), "%s: a tensor is not 16-byte aligned", what);
+  HTRVT_REQUIRE(!misaligned16(x, dy), "%s: a tensor is not 16-byte aligned", what);
   const Geo g = make_geo(W, C, kh, kw, dil, dtype);
   const dim3 grid(g.gx, wgrad_chunks(B, H, g), H);
 #define LAUNCH(KK)                                                                                                       \
@@ -491,7 +488,7 @@ extern "C" int htrvt_van_moments(const void* x, float* partial, int64_t rows, in
   const char* what = "htrvt_van_moments";
   if (check_rows(what, rows, C, dtype)) return -1;
   HTRVT_REQUIRE(x && partial, "%s: null buffer", what);
-  HTRVT_REQUIRE(aligned16(x), "%s: x is not 16-byte aligned", what);
+  HTRVT_REQUIRE(!misaligned16(x), "%s: x is not 16-byte aligned", what);
   const RowGrid g = row_grid(rows, C, dtype, 1, 128);
   if (dtype == HTRVT_BF16)
     hipLaunchKernelGGL(moments_kernel<bf16_t>, g.grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, partial,

@@ -116,21 +116,32 @@ def test_local_attention_other_windows(w, hd, dtype):
     at a time: an odd window's last row goes with weight 0 for its partner)"""
     from htrvt_amd import variants as V
     assert V.local_attention_supported(hd, w, dtype)
-    B, N, h = 2, 100, 2
-    qkv, bias, dout = _local_inputs(B, N, h, hd, dtype, 40 + w + hd)
+    _check_local(2, 100, 2, hd, w, dtype, 40 + w + hd)
+
+
+def _check_local(B, N, h, hd, w, dtype, seed):
+    qkv, bias, dout = _local_inputs(B, N, h, hd, dtype, seed)
     qr = qkv.double().requires_grad_(True)
     br = bias.double().requires_grad_(True)
     ref = _ref_local(qr, br, B, N, h, hd, w)
     ref.backward(dout.double())
     out, dq, db = _run_local(qkv, bias, dout, B, N, h, w, dtype)
     err = (out.double().cpu() - ref.detach()).abs().max().item()
-    print(f"w={w} hd={hd} {dtype}: out max-abs {err:.3e}")
+    print(f"N={N} w={w} hd={hd} {dtype}: out max-abs {err:.3e}")
     assert err < (2.5e-2 if dtype == torch.bfloat16 else 2e-5), err
     _gate("dqkv", dq, qr.grad, **_grad_gate(dtype))
     if N % w:
         _gate("dbias", db[h * hd:], br.grad[h * hd:], **_grad_gate(dtype))
     else:
         assert float(db.abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+@pytest.mark.parametrize("hd", (64, 128))
+def test_local_attention_fewer_units_than_waves(hd, dtype):
+    """one image, one head, 20 tokens in windows of 12: two units, the second ragged with four padding slots, in workgroups
+    of up to four waves -- the waves past the last unit must stage and write nothing"""
+    _check_local(1, 20, 1, hd, 12, dtype, 77 + hd)
 
 
 @pytest.mark.parametrize("N", (96, 240))
