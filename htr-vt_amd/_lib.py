@@ -184,6 +184,9 @@ PROTOTYPES = {
     "htrvt_attn_win2d_fwd": (i32, [vp, vp, vp] + [i32] * 9 + [f32, i32, vp]),
     "htrvt_attn_win2d_rows": (i32, [i32] * 6),
     "htrvt_attn_win2d_bwd": (i32, [vp] * 5 + [i32] * 9 + [f32, i32, vp]),
+    "htrvt_attn_nbr2d_supported": (i32, [i32, i32, i32, i32]),
+    "htrvt_attn_nbr2d_fwd": (i32, [vp, vp, vp] + [i32] * 7 + [f32, i32, vp]),
+    "htrvt_attn_nbr2d_bwd": (i32, [vp] * 5 + [i32] * 7 + [f32, i32, vp]),
 }
 
 

@@ -1,10 +1,10 @@
 """The launch sequences of the attention flavours, norms, the convolutional token mixer, the VAN forks' height reducer
-and horizontal mixer and the Swin fork's blocks, each written once.
+and horizontal mixer, the Swin fork's blocks and the SVTR fork's mixing blocks, each written once.
 
 Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
 torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
-here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, swin.py, and the autograd wrappers of
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, swin.py, svtr.py, and the autograd wrappers of
 variants.py.
 
 Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5.
@@ -16,7 +16,7 @@ backward takes the forward's `drop`.  drop=None is the call without dropout, unt
 import torch
 
 from ._lib import check, lib
-from .ops import MNMAJOR, colsum, dt, gemm, ptr, stream
+from .ops import GATHER_CONV_DGRAD, GATHER_CONV_FWD, GATHER_CONV_WGRAD, MNMAJOR, ConvGeom, colsum, cpad, dt, gemm, ptr, stream
 
 
 def _f32(x, *shape):
@@ -782,3 +782,163 @@ def window_attention_bwd(dy, x, P, saved, Bn, h, window):
                                dtable=G["relative_position_bias_table"])
     G["qkv.weight"], G["qkv.bias"] = _pw_wgrad(dqkv, x)
     return _pw_dgrad(dqkv, P["qkv.weight"]), G
+
+
+# ---- SVTR fork (csrc/svtr.hip): MultiHeadSelfAttention, MixingBlock and Merging of model_sgm_mms_svtr/model/svtr.py (its -----
+# Combining is the Swin fork's: combining_fwd / _bwd above).  Rows and P as in the Swin section; the fork's qkv Linear has no
+# bias.  A local block's attention is the neighbourhood kernel; a global block's is the fused kernel of csrc/attention.hip in
+# bfloat16 and the unfused GEMM route otherwise.
+
+def nbr2d_attention_fwd(qkv, B, H, W, h, kernel, save=True):
+    """every query (y, x) of the [H, W] token map over the keys of its centred kernel = (kh, kw) box, clipped to the map ->
+    (out [B*H*W, D], lse float32 [B*h, H*W] or None)"""
+    D, hd = _heads(qkv, h)
+    out = _like(qkv, B * H * W, D)
+    lse = _f32(qkv, B * h, H * W) if save else None
+    check(lib.htrvt_attn_nbr2d_fwd(ptr(qkv), ptr(out), ptr(lse), B, H, W, h, hd, kernel[0], kernel[1], hd ** -0.5,
+                                   dt(qkv.dtype), stream()), "attn_nbr2d_fwd")
+    return out, lse
+
+
+def nbr2d_attention_bwd(qkv, out, dout, lse, B, H, W, h, kernel):
+    """dqkv by the recomputing backward (two launches: dq, then dk / dv); no workspace"""
+    hd = _heads(qkv, h)[1]
+    dqkv = torch.empty_like(qkv)
+    check(lib.htrvt_attn_nbr2d_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, H, W, h, hd, kernel[0], kernel[1],
+                                   hd ** -0.5, dt(qkv.dtype), stream()), "attn_nbr2d_bwd")
+    return dqkv
+
+
+def _global_fused(qkv, N):
+    """a global block's route: the fused kernel serves bfloat16 and N >= 32"""
+    return qkv.dtype == torch.bfloat16 and N >= 32
+
+
+def _mixing_attention_fwd(qkv, B, H, W, h, kernel, save):
+    """-> (a, what the backward takes: lse, or the unfused route's P)"""
+    if kernel is not None:
+        return nbr2d_attention_fwd(qkv, B, H, W, h, kernel, save)
+    if _global_fused(qkv, H * W):
+        return attention_fwd(qkv, B, H * W, h, save=save)
+    return attention_unfused_fwd(qkv, B, H * W, h)
+
+
+def _mixing_attention_bwd(qkv, a, da, aux, B, H, W, h, kernel):
+    if kernel is not None:
+        return nbr2d_attention_bwd(qkv, a, da, aux, B, H, W, h, kernel)
+    if _global_fused(qkv, H * W):
+        return attention_bwd(qkv, a, da, aux, B, H * W, h)
+    return attention_unfused_bwd(qkv, aux, da, B, H * W, h)
+
+
+def mha_fwd(x, P, B, H, W, h, kernel, save=True):
+    """MultiHeadSelfAttention on x [B*H*W, C]: proj(attention(qkv(x))), kernel = (kh, kw) for a local module, None for a
+    global one -> (y, saved)"""
+    qkv = _pw(x, P["qkv.weight"])
+    a, aux = _mixing_attention_fwd(qkv, B, H, W, h, kernel, save)
+    return _pw(a, P["proj.weight"], bias=P["proj.bias"]), (qkv, a, aux)
+
+
+def mha_bwd(dy, x, P, saved, B, H, W, h, kernel):
+    qkv, a, aux = saved
+    G = {}
+    G["proj.weight"], G["proj.bias"] = _pw_wgrad(dy, a)
+    dqkv = _mixing_attention_bwd(qkv, a, _pw_dgrad(dy, P["proj.weight"]), aux, B, H, W, h, kernel)
+    G["qkv.weight"] = _pw_wgrad(dqkv, x, bias=False)[0]
+    return _pw_dgrad(dqkv, P["qkv.weight"]), G
+
+
+def mixing_block_fwd(x, P, B, H, W, h, kernel, eps=1e-5, save=True):
+    """MixingBlock on x [B*H*W, C]: x1 = x + proj(attention(qkv(norm1(x)))), y = x1 + mlp.2(gelu(mlp.0(norm2(x1)))) ->
+    (y, saved).  kernel = (kh, kw): a local block, the neighbourhood kernel.  kernel = None: a global block -- bfloat16 with
+    H*W >= 32 through the fused attention kernel, float32 (and bfloat16 with fewer than 32 tokens) through the unfused
+    route, which keeps a [B*h, N, N] P for the backward and is the parity route only"""
+    n1, mean1, rstd1 = layernorm_fwd(x, P["norm1.weight"], P["norm1.bias"], eps, save)
+    qkv = _pw(n1, P["attn.qkv.weight"])
+    a, aux = _mixing_attention_fwd(qkv, B, H, W, h, kernel, save)
+    x1 = _pw(a, P["attn.proj.weight"], bias=P["attn.proj.bias"], residual=x)
+    n2, mean2, rstd2 = layernorm_fwd(x1, P["norm2.weight"], P["norm2.bias"], eps, save)
+    pre = _like(x, x.shape[0], P["mlp.0.weight"].shape[0])
+    hid = _pw(n2, P["mlp.0.weight"], bias=P["mlp.0.bias"], act=1, preact=pre)
+    y = _pw(hid, P["mlp.2.weight"], bias=P["mlp.2.bias"], residual=x1)
+    return y, (n1, mean1, rstd1, qkv, a, aux, x1, n2, mean2, rstd2, pre, hid)
+
+
+def mixing_block_bwd(dy, x, P, saved, B, H, W, h, kernel):
+    """dy [B*H*W, C] -> (dx, {parameter gradients by the fork's names, float32})"""
+    n1, mean1, rstd1, qkv, a, aux, x1, n2, mean2, rstd2, pre, hid = saved
+    G = {}
+    G["mlp.2.weight"], G["mlp.2.bias"] = _pw_wgrad(dy, hid)
+    dpre = _gelu_bwd(_pw_dgrad(dy, P["mlp.2.weight"]), pre)
+    G["mlp.0.weight"], G["mlp.0.bias"] = _pw_wgrad(dpre, n2)
+    dx1, G["norm2.weight"], G["norm2.bias"] = _ln_bwd(_pw_dgrad(dpre, P["mlp.0.weight"]), x1, mean2, rstd2, P["norm2.weight"],
+                                                      dres=dy)
+    G["attn.proj.weight"], G["attn.proj.bias"] = _pw_wgrad(dx1, a)
+    dqkv = _mixing_attention_bwd(qkv, a, _pw_dgrad(dx1, P["attn.proj.weight"]), aux, B, H, W, h, kernel)
+    G["attn.qkv.weight"] = _pw_wgrad(dqkv, n1, bias=False)[0]
+    dx, G["norm1.weight"], G["norm1.bias"] = _ln_bwd(_pw_dgrad(dqkv, P["attn.qkv.weight"]), x, mean1, rstd1, P["norm1.weight"],
+                                                     dres=dx1)
+    return dx, G
+
+
+def svtr_merge_geom(B, H, W, Ci, Co):
+    """the Merging convolution: 3x3, stride (2, 1), padding 1 on the NHWC map; Ho = (H - 1) // 2 + 1"""
+    return ConvGeom(B, H, W, Ci, Co, 3, (2, 1), 1)
+
+
+def svtr_merge_packs(w, dtype):
+    """Conv2d weight [Co, Ci, 3, 3] -> the conv gather descriptors' operands (torch copies): the forward pack
+    [Co][9][cpad(Ci)] and the dgrad pack [Ci][9][cpad(Co)], tap = 3 ky + kx, the padding channels zero"""
+    Co, Ci = w.shape[:2]
+    taps = w.reshape(Co, Ci, 9)
+    fwd = torch.zeros(Co, 9, cpad(Ci, dtype), dtype=dtype, device=w.device)
+    dgr = torch.zeros(Ci, 9, cpad(Co, dtype), dtype=dtype, device=w.device)
+    fwd[:, :, :Ci] = taps.permute(0, 2, 1)
+    dgr[:, :, :Co] = taps.permute(1, 2, 0)
+    return fwd, dgr
+
+
+def _dgrad_by_class(g, dtype):
+    """one launch per input-row parity class, each over the taps that reach it: the form the bfloat16 LDS-DMA kernels
+    serve, for classes of more than 128 pixels; otherwise one launch over every pixel and tap"""
+    return dtype == torch.bfloat16 and all(g.B * Hq * Wq > 128 for _a, _b, _nt, Hq, Wq in g.parity_classes())
+
+
+def svtr_merge_fwd(x, P, B, H, W, eps=1e-5, save=True):
+    """Merging on x [B*H*W, C], which is the NHWC map: norm(conv(x) + bias) with the convolution gathered by htrvt_gemm
+    (GATHER_CONV_FWD), the bias in its epilogue.  P["conv.weight"]: (forward pack, dgrad pack) of svtr_merge_packs ->
+    (y [B*Ho*W, Cout], saved)"""
+    wf = P["conv.weight"][0]
+    g = svtr_merge_geom(B, H, W, x.shape[1], wf.shape[0])
+    cpi = cpad(g.Ci, x.dtype)
+    z = _like(x, B * g.Ho * g.Wo, g.Co)
+    gemm(x, wf, z, dtype=x.dtype, M=B * g.Ho * g.Wo, N=g.Co, K=g.taps * cpi, lda=g.Ci, ldb=g.taps * cpi, ldc=g.Co,
+         gather=GATHER_CONV_FWD, geom=g, Cpad=cpi, bias=P["conv.bias"])
+    y, mean, rstd = layernorm_fwd(z, P["norm.weight"], P["norm.bias"], eps, save)
+    return y, (z, mean, rstd)
+
+
+def svtr_merge_bwd(dy, x, P, saved, B, H, W):
+    """dy [B*Ho*W, Cout] -> (dx [B*H*W, C], {"conv.weight": float32 [Cout, C, 3, 3], "conv.bias", "norm.weight",
+    "norm.bias"}): the weight gradient by GATHER_CONV_WGRAD in the descriptor's [9][cpad(C)][Cout] form and copied back, the
+    bias gradient the column sums of dz, dx by GATHER_CONV_DGRAD"""
+    z, mean, rstd = saved
+    wd = P["conv.weight"][1]
+    g = svtr_merge_geom(B, H, W, x.shape[1], z.shape[1])
+    M = B * g.Ho * g.Wo
+    cpi, cpo = cpad(g.Ci, x.dtype), cpad(g.Co, x.dtype)
+    dz, dgamma, dbeta = _ln_bwd(dy, z, mean, rstd, P["norm.weight"])
+    db = torch.zeros(g.Co, dtype=torch.float32, device=x.device)
+    colsum(dz, M, g.Co, g.Co, db, dti=dt(dz.dtype))
+    packed = torch.zeros(g.taps, cpi, g.Co, dtype=torch.float32, device=x.device)
+    gemm(x, dz, packed, dtype=x.dtype, M=g.taps * cpi, N=g.Co, K=M, lda=g.Ci, ldb=g.Co, ldc=g.Co, a_layout=MNMAJOR,
+         b_layout=MNMAJOR, gather=GATHER_CONV_WGRAD, geom=g, Cpad=cpi, accumulate=True, c_f32=True)
+    dw = packed[:, :g.Ci].permute(2, 1, 0).reshape(g.Co, g.Ci, 3, 3).contiguous()
+    dx = _like(x, B * H * W, g.Ci)
+    kw = dict(dtype=x.dtype, N=g.Ci, lda=g.Co, ldb=g.taps * cpo, ldc=g.Ci, gather=GATHER_CONV_DGRAD, geom=g, Cpad=cpo)
+    if _dgrad_by_class(g, x.dtype):
+        for a, b, nt, Hq, Wq in g.parity_classes():
+            gemm(dz, wd, dx, M=B * Hq * Wq, K=nt * cpo, cls=(a, b), **kw)
+    else:
+        gemm(dz, wd, dx, M=B * H * W, K=g.taps * cpo, **kw)
+    return dx, {"conv.weight": dw, "conv.bias": db, "norm.weight": dgamma, "norm.bias": dbeta}

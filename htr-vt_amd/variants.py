@@ -500,3 +500,41 @@ def window_attention_2d(qkv, table, B, H, W, heads, window, shift=(0, 0)):
     if not win2d_supported(qkv.shape[1] // 3 // heads, window, qkv.dtype):
         raise ValueError(f"window attention: {lib.htrvt_last_error().decode()}")
     return _WindowAttention2D.apply(qkv, table, B, H, W, heads, window, shift)
+
+
+# ---- SVTR fork (model_sgm_mms_svtr/model/svtr.py MultiHeadSelfAttention with local=True): 2-D neighbourhood attention,
+# csrc/svtr.hip
+
+class _NeighborhoodAttention2D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, B, H, W, heads, kernel):
+        qkv = qkv.contiguous()
+        out, lse = seq_ops.nbr2d_attention_fwd(qkv, B, H, W, heads, kernel, save=True)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.dims = (B, H, W, heads, kernel)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        return (seq_ops.nbr2d_attention_bwd(qkv, out, dout.contiguous().to(qkv.dtype), lse, *ctx.dims),) + (None,) * 5
+
+
+def nbr2d_supported(head_dim, kernel, dtype):
+    return bool(lib.htrvt_attn_nbr2d_supported(head_dim, kernel[0], kernel[1], dt(dtype)))
+
+
+def neighborhood_attention_2d(qkv, B, H, W, heads, kernel=(7, 11)):
+    """The attention of the SVTR fork's local MultiHeadSelfAttention, on its qkv Linear's output: qkv [B*H*W, 3*heads*hd]
+    (float32 or bfloat16, hd 32 / 64) in plain token order -> [B*H*W, heads*hd].  Query (y, x) of the [H, W] map attends to the
+    keys within kernel[0] // 2 rows and kernel[1] // 2 columns of it (kernel odd, at most (7, 11)); keys outside the map do not
+    exist.  Differentiable in qkv; the gradient is bitwise reproducible."""
+    _need_device(qkv)
+    kernel = tuple(int(v) for v in kernel)
+    # the kernels see pointers only: a shape that disagrees with (B, H, W, heads) would send them past a buffer
+    if qkv.dim() != 2 or heads < 1 or B < 0 or H < 1 or W < 1 or qkv.shape[0] != B * H * W or qkv.shape[1] % (3 * heads):
+        raise ValueError(f"neighborhood_attention_2d: qkv [B*H*W = {B * H * W}, 3*heads*hd] expected for heads = {heads}, got "
+                         f"{tuple(qkv.shape)}")
+    if len(kernel) != 2 or not nbr2d_supported(qkv.shape[1] // 3 // heads, kernel, qkv.dtype):
+        raise ValueError(f"neighbourhood attention: {lib.htrvt_last_error().decode()}")
+    return _NeighborhoodAttention2D.apply(qkv, B, H, W, heads, kernel)

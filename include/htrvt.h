@@ -730,6 +730,27 @@ int htrvt_attn_win2d_rows(int B, int H, int W, int heads, int wh, int ww);
 int htrvt_attn_win2d_bwd(const void* qkv, const float* table, const void* dout, void* dqkv, float* dtable_partial, int B, int H,
                          int W, int heads, int hd, int wh, int ww, int sh, int sw, float scale, int dtype, void* stream);
 
+/* ---- SVTR fork (csrc/svtr.hip): MultiHeadSelfAttention(local=True) of model_sgm_mms_svtr/model/svtr.py, between the qkv and
+ * proj Linear layers: 2-D neighbourhood attention.  Query (h, w) of the H x W token map attends to the keys (h', w') of the
+ * map with |h - h'| <= kh / 2 and |w - w'| <= kw / 2 (integer halves) -- the fork's dense scores plus its -inf mask, where a
+ * masked key has weight exactly 0.  Keys outside the map do not exist: they are never read and contribute nothing.
+ *   qkv [B H W][3][heads][hd] in plain token order (b, h, w), as the (bias-free) qkv GEMM leaves it; out, dout [B H W][heads][hd];
+ *   dqkv as qkv.  lse float32 [B heads][H W]: log sum_k exp(scale q.k) over the query's keys; NULL in a forward-only call.
+ *   out = sum_k softmax_k(scale q.k) v_k.
+ *   _bwd recomputes P = exp(scale q.k - lse) from qkv and lse, forms delta = dO . out itself (no workspace) and writes dqkv
+ *   whole, in two launches of one kernel: dq over each query's box, then dk / dv over each key's box (the box is symmetric,
+ *   so the queries that see a key are the key's own box).  No float atomics: two runs give the same bits.
+ *   Served: float32 and bfloat16, hd 32 / 64, kh and kw odd with 1 <= kh <= 7, 1 <= kw <= 11, any H, W >= 1 (H < kh and
+ *   W < kw included), any B >= 0 and heads >= 1, base pointers 16-byte aligned.  Offsets are 64-bit, so the operands may pass
+ *   2 GiB; the bound is the grid: B heads ceil(H / 4) ceil(W / 16) workgroups must stay below 2^31.  Everything else: a
+ *   non-zero return, the reason in htrvt_last_error(), nothing launched.  _supported: 1 if (hd, kh, kw, dtype) is served,
+ *   else 0 with the reason set. */
+int htrvt_attn_nbr2d_supported(int hd, int kh, int kw, int dtype);
+int htrvt_attn_nbr2d_fwd(const void* qkv, void* out, float* lse, int B, int H, int W, int heads, int hd, int kh, int kw,
+                         float scale, int dtype, void* stream);
+int htrvt_attn_nbr2d_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int H, int W,
+                         int heads, int hd, int kh, int kw, float scale, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
