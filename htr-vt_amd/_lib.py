@@ -167,6 +167,27 @@ PROTOTYPES = {
     "htrvt_mixer_fwd_eval": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_mixer_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "htrvt_mixer_bwd": (i32, [vp] * 10 + [i32, i32, i32, i32, i32, vp]),
+    "htrvt_gnmixer_rows": (i32, [i32, i32, i32, i32]),
+    "htrvt_gnmixer_parts": (i32, [i32, i32, i32, i32]),
+    "htrvt_gnmixer_fwd": (i32, [vp] * 5 + [i32] * 5 + [vp]),
+    "htrvt_gn_finalize": (i32, [vp, i32, i32, f64, f32, vp, vp, vp]),
+    "htrvt_gnmixer_act": (i32, [vp] * 6 + [i32] * 4 + [vp]),
+    "htrvt_gnmixer_bwd_reduce": (i32, [vp] * 8 + [i32] * 4 + [vp]),
+    "htrvt_gn_bwd_finalize": (i32, [vp, i32, i32, f64, vp, vp, vp]),
+    "htrvt_gnmixer_bwd": (i32, [vp] * 13 + [i32] * 5 + [vp]),
+    "htrvt_se_mean": (i32, [vp, vp] + [i32] * 4 + [vp]),
+    "htrvt_se_mlp_fwd": (i32, [vp] * 8 + [i32] * 3 + [vp]),
+    "htrvt_se_scale_fwd": (i32, [vp] * 3 + [i32] * 4 + [vp]),
+    "htrvt_se_scale_bwd_reduce": (i32, [vp] * 3 + [i32] * 4 + [vp]),
+    "htrvt_se_mlp_bwd": (i32, [vp] * 8 + [i32] * 3 + [vp]),
+    "htrvt_se_wgrad": (i32, [vp] * 4 + [i32] * 3 + [vp]),
+    "htrvt_se_scale_bwd": (i32, [vp] * 4 + [i32] * 4 + [vp]),
+    "htrvt_seq_down2_fwd": (i32, [vp, vp] + [i32] * 4 + [vp]),
+    "htrvt_seq_down2_bwd": (i32, [vp, vp] + [i32] * 4 + [vp]),
+    "htrvt_seq_up_add_fwd": (i32, [vp] * 3 + [i32] * 5 + [vp]),
+    "htrvt_seq_up_add_bwd": (i32, [vp, vp] + [i32] * 5 + [vp]),
+    "htrvt_silu_fwd": (i32, [vp, vp, i64, i32, vp]),
+    "htrvt_silu_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
     "htrvt_van_dw_fwd": (i32, [vp, vp, vp] + [i32] * 8 + [vp]),
     "htrvt_van_dw_bwd_input": (i32, [vp, vp, vp, vp] + [i32] * 8 + [vp]),
     "htrvt_van_dw_rows": (i32, [i32] * 8),

@@ -1,10 +1,11 @@
 """The launch sequences of the attention flavours, norms, the convolutional token mixer, the VAN forks' height reducer
-and horizontal mixer, the Swin fork's blocks and the SVTR fork's mixing blocks, each written once.
+and horizontal mixer, the Swin fork's blocks, the SVTR fork's mixing blocks and the convolutional forks' Conformer /
+SqueezeFormer blocks, each written once.
 
 Plain functions over device tensors: no autograd, no Engine state.  They launch on the current stream, allocate with
 torch.empty on their input's device, and a forward returns what its backward takes (P or lse, mean / rstd).  Gradient
 destinations that the kernels ADD into (dtable, dbias, dgamma / dbeta, dalpha) come from the caller and are not zeroed
-here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, swin.py, svtr.py, and the autograd wrappers of
+here.  Callers: engine.py (the four models), sgm/model/sgm_head.py, mixer.py, van.py, swin.py, svtr.py, conformer.py, and the autograd wrappers of
 variants.py.
 
 Self-attention reads qkv [B*N, 3*D] in the qkv Linear's layout [B, N, 3, h, hd]; the score scale is hd^-0.5.
@@ -942,3 +943,322 @@ def svtr_merge_bwd(dy, x, P, saved, B, H, W):
     else:
         gemm(dz, wd, dx, M=B * H * W, K=g.taps * cpo, **kw)
     return dx, {"conv.weight": dw, "conv.bias": db, "norm.weight": dgamma, "norm.bias": dbeta}
+
+
+# ---- convolutional forks (csrc/gnmixer.hip): ConvModule, FeedForward, SqueezeExcite1D, Downsample1D, Upsample1D and the
+# blocks of model_sgm_mms_conv/model/HTR_VT.py and model_sgm_mms_conv_squeeze/model/HTR_VT.py on rows [B*N, D].  P maps the
+# fork's parameter names to tensors: Linear and 1x1 Conv1d weights as [out, in] in the activations' dtype, everything else
+# (biases, norms, the depthwise weight [C, 1, k], the excite MLP) float32 as stored.
+
+def gn_mixer_fwd(u, weight, bias, gamma, beta, B, N, eps=1e-5):
+    """u [B*N, 2*C] (pointwise_conv1's output), weight float32 [C, 1, k] -> (s [B*N, C], (c, mean, rstd)):
+    s = silu(GroupNorm(1, C)(dwconv(glu(u)) + bias)), the statistics float32 [B] over the C * N values of each image"""
+    C, k, dti, st = u.shape[1] // 2, weight.shape[-1], dt(u.dtype), stream()
+    parts = lib.htrvt_gnmixer_parts(B, N, C, dti)
+    if parts < 0:
+        check(-1, "gnmixer_fwd")
+    c, pairs, mean, rstd = _like(u, B * N, C), _f32(u, B, parts, 2), _f32(u, B), _f32(u, B)
+    check(lib.htrvt_gnmixer_fwd(ptr(u), ptr(weight), ptr(bias), ptr(c), ptr(pairs), B, N, C, k, dti, st), "gnmixer_fwd")
+    check(lib.htrvt_gn_finalize(ptr(pairs), B, parts, float(C * N), eps, ptr(mean), ptr(rstd), st), "gn_finalize")
+    return gn_mixer_act(c, mean, rstd, gamma, beta, B, N), (c, mean, rstd)
+
+
+def gn_mixer_act(c, mean, rstd, gamma, beta, B, N, s=None):
+    """s = silu((c - mean_b) * rstd_b * gamma + beta): the forward's last pass, and the backward's way to s without keeping it"""
+    s = torch.empty_like(c) if s is None else s
+    check(lib.htrvt_gnmixer_act(ptr(c), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(s), B, N, c.shape[1], dt(c.dtype),
+                                stream()), "gnmixer_act")
+    return s
+
+
+def gn_mixer_bwd(ds, u, weight, gamma, beta, B, N, saved):
+    """ds [B*N, C] -> (du [B*N, 2*C], dweight [C, 1, k], dbias, dgamma, dbeta), float32 parameter gradients"""
+    c, mean, rstd = saved
+    C, k, dti, st = u.shape[1] // 2, weight.shape[-1], dt(u.dtype), stream()
+    rows, parts = lib.htrvt_gnmixer_rows(B, N, C, dti), lib.htrvt_gnmixer_parts(B, N, C, dti)
+    if rows < 0 or parts < 0:
+        check(-1, "gnmixer_bwd")
+    pc, pairs, m1, m2 = _f32(u, rows, 2 * C), _f32(u, B, parts, 2), _f32(u, B), _f32(u, B)
+    check(lib.htrvt_gnmixer_bwd_reduce(ptr(ds), ptr(c), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(pc), ptr(pairs), B, N, C,
+                                       dti, st), "gnmixer_bwd_reduce")
+    check(lib.htrvt_gn_bwd_finalize(ptr(pairs), B, parts, float(C * N), ptr(m1), ptr(m2), st), "gn_bwd_finalize")
+    dnorm = torch.zeros(2 * C, dtype=torch.float32, device=u.device)       # (d beta | d gamma): one column-sum launch
+    colsum(pc, rows, 2 * C, 2 * C, dnorm, dti=0)
+    pw, pb, du = _f32(u, rows, C * k), _f32(u, rows, C), torch.empty_like(u)
+    check(lib.htrvt_gnmixer_bwd(ptr(u), ptr(c), ptr(ds), ptr(weight), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(m1),
+                                ptr(m2), ptr(du), ptr(pw), ptr(pb), B, N, C, k, dti, st), "gnmixer_bwd")
+    dweight = torch.zeros_like(weight)
+    colsum(pw, rows, C * k, C * k, dweight, dti=0)
+    dbias = torch.zeros(C, dtype=torch.float32, device=u.device)
+    colsum(pb, rows, C, C, dbias, dti=0)
+    return du, dweight, dbias, dnorm[C:], dnorm[:C]
+
+
+def se_fwd(x, w1, b1, w2, b2, B, N):
+    """SqueezeExcite1D on x [B*N, D]: y = x * g[b], g = sigmoid(fc2(silu(fc1(mean over the tokens)))); the MLP (w1 [H, D],
+    w2 [D, H], float32) runs in float32 -> (y, (mean [B, D], pre [B, H], act [B, H], g [B, D]))"""
+    D, H, dti, st = x.shape[1], w1.shape[0], dt(x.dtype), stream()
+    mean, pre, act, g, y = _f32(x, B, D), _f32(x, B, H), _f32(x, B, H), _f32(x, B, D), torch.empty_like(x)
+    check(lib.htrvt_se_mean(ptr(x), ptr(mean), B, N, D, dti, st), "se_mean")
+    check(lib.htrvt_se_mlp_fwd(ptr(mean), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(pre), ptr(act), ptr(g), B, D, H, st), "se_mlp_fwd")
+    check(lib.htrvt_se_scale_fwd(ptr(x), ptr(g), ptr(y), B, N, D, dti, st), "se_scale_fwd")
+    return y, (mean, pre, act, g)
+
+
+def se_bwd(dy, x, w1, w2, B, N, saved):
+    """dy [B*N, D] -> (dx, (dw1, db1, dw2, db2)), the weight gradients summed over the images in order"""
+    mean, pre, act, g = saved
+    D, H, dti, st = x.shape[1], w1.shape[0], dt(x.dtype), stream()
+    dg, dh2, dh1, dmean = _f32(x, B, D), _f32(x, B, D), _f32(x, B, H), _f32(x, B, D)
+    check(lib.htrvt_se_scale_bwd_reduce(ptr(dy), ptr(x), ptr(dg), B, N, D, dti, st), "se_scale_bwd_reduce")
+    check(lib.htrvt_se_mlp_bwd(ptr(dg), ptr(g), ptr(pre), ptr(w1), ptr(w2), ptr(dh2), ptr(dh1), ptr(dmean), B, D, H, st), "se_mlp_bwd")
+    dw2, db2, dw1, db1 = _f32(x, D, H), _f32(x, D), _f32(x, H, D), _f32(x, H)
+    check(lib.htrvt_se_wgrad(ptr(dh2), ptr(act), ptr(dw2), ptr(db2), B, D, H, st), "se_wgrad")
+    check(lib.htrvt_se_wgrad(ptr(dh1), ptr(mean), ptr(dw1), ptr(db1), B, H, D, st), "se_wgrad")
+    dx = torch.empty_like(x)
+    check(lib.htrvt_se_scale_bwd(ptr(dy), ptr(g), ptr(dmean), ptr(dx), B, N, D, dti, st), "se_scale_bwd")
+    return dx, (dw1, db1, dw2, db2)
+
+
+def seq_down2_fwd(x, B, N):
+    """Downsample1D on x [B*N, D]: the mean of tokens 2j and 2j + 1 -> [B*(N // 2), D]; N <= 1 is the identity"""
+    if N <= 1:
+        return x
+    y = _like(x, B * (N // 2), x.shape[1])
+    check(lib.htrvt_seq_down2_fwd(ptr(x), ptr(y), B, N, x.shape[1], dt(x.dtype), stream()), "seq_down2_fwd")
+    return y
+
+
+def seq_down2_bwd(dy, B, N):
+    """dy [B*(N // 2), D] -> dx [B*N, D]; an odd last token gets zero"""
+    if N <= 1:
+        return dy
+    dx = _like(dy, B * N, dy.shape[1])
+    check(lib.htrvt_seq_down2_bwd(ptr(dy), ptr(dx), B, N, dy.shape[1], dt(dy.dtype), stream()), "seq_down2_bwd")
+    return dx
+
+
+def seq_up_add_fwd(y, skip, B, n, N0):
+    """Upsample1D fused with the encoder's skip add: out[b, i] = y[b, (i * n) // N0] + skip[b, i] -> [B*N0, D]"""
+    out = torch.empty_like(skip)
+    check(lib.htrvt_seq_up_add_fwd(ptr(y), ptr(skip), ptr(out), B, n, N0, y.shape[1], dt(y.dtype), stream()), "seq_up_add_fwd")
+    return out
+
+
+def seq_up_add_bwd(dout, B, n, N0):
+    """dout [B*N0, D] -> dy [B*n, D], each source token's targets summed in order (the skip's gradient is dout itself)"""
+    dy = _like(dout, B * n, dout.shape[1])
+    check(lib.htrvt_seq_up_add_bwd(ptr(dout), ptr(dy), B, n, N0, dout.shape[1], dt(dout.dtype), stream()), "seq_up_add_bwd")
+    return dy
+
+
+def silu(pre):
+    a = torch.empty_like(pre)
+    check(lib.htrvt_silu_fwd(ptr(pre), ptr(a), pre.numel(), dt(pre.dtype), stream()), "silu_fwd")
+    return a
+
+
+def silu_bwd(da, pre):
+    dpre = torch.empty_like(pre)
+    check(lib.htrvt_silu_bwd(ptr(da), ptr(pre), ptr(dpre), pre.numel(), dt(pre.dtype), stream()), "silu_bwd")
+    return dpre
+
+
+def silu_ffn_fwd(x, w1, b1, w2, b2, alpha=1.0, residual=None):
+    """FeedForward on x [rows, D]: alpha * lin2(silu(lin1(x))) (+ residual) -> (y, (pre,)); alpha rides in the second GEMM's
+    descriptor (the bias scaled to match), the activation is kept as lin1's output only"""
+    pre = _pw(x, w1, bias=b1)
+    y = _pw(silu(pre), w2, bias=b2 if alpha == 1.0 else b2 * alpha, alpha=alpha, residual=residual)
+    return y, (pre,)
+
+
+def silu_ffn_bwd(dy, x, w1, w2, saved, alpha=1.0):
+    """dy [rows, D] (the gradient at y) -> (dx, (dw1, db1, dw2, db2))"""
+    (pre,) = saved
+    dw2, db2 = _pw_wgrad(dy, silu(pre))
+    if alpha != 1.0:
+        dw2, db2 = dw2.mul_(alpha), db2.mul_(alpha)
+    dpre = silu_bwd(_pw_dgrad(dy, w2, alpha=alpha), pre)
+    dw1, db1 = _pw_wgrad(dpre, x)
+    return _pw_dgrad(dpre, w1), (dw1, db1, dw2, db2)
+
+
+def _sub(P, prefix):
+    return {n[len(prefix):]: t for n, t in P.items() if n.startswith(prefix)}
+
+
+def _put(G, prefix, names, grads):
+    for n, g in zip(names, grads):
+        G[prefix + n] = g
+
+
+FFN_NAMES = ("lin1.weight", "lin1.bias", "lin2.weight", "lin2.bias")
+
+
+def conv_module_fwd(x, P, B, N, eps=1e-5, gn_eps=1e-5, drop=None, save=True):
+    """ConvModule on x [B*N, D]: x + dropout(pointwise_conv2(silu(GroupNorm(dwconv(glu(pointwise_conv1(LayerNorm(x)))))))).
+    drop: None or (seeds, p), seeds an int64 device tensor of two elements (the mask is redrawn from it in the backward) ->
+    (y, (t, mean, rstd, u, c, gn_mean, gn_rstd))"""
+    t, mean, rstd = layernorm_fwd(x, P["layer_norm.weight"], P["layer_norm.bias"], eps, save)
+    u = _pw(t, P["pointwise_conv1.weight"], bias=P["pointwise_conv1.bias"])
+    s, gn = gn_mixer_fwd(u, P["depthwise_conv.weight"], P["depthwise_conv.bias"], P["norm.weight"], P["norm.bias"], B, N, gn_eps)
+    if drop is None:
+        y = _pw(s, P["pointwise_conv2.weight"], bias=P["pointwise_conv2.bias"], residual=x)
+    else:
+        y = residual_dropout(_pw(s, P["pointwise_conv2.weight"], bias=P["pointwise_conv2.bias"]), x, N, drop[0], drop[1], 0.0)
+    return y, (t, mean, rstd, u) + gn
+
+
+def conv_module_bwd(dy, x, P, saved, B, N, drop=None):
+    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32})"""
+    t, mean, rstd, u, c, gmean, grstd = saved
+    G = {}
+    do = dy if drop is None else residual_dropout(dy, None, N, drop[0], drop[1], 0.0)
+    s = gn_mixer_act(c, gmean, grstd, P["norm.weight"], P["norm.bias"], B, N)
+    G["pointwise_conv2.weight"], G["pointwise_conv2.bias"] = _pw_wgrad(do, s)
+    du, G["depthwise_conv.weight"], G["depthwise_conv.bias"], G["norm.weight"], G["norm.bias"] = gn_mixer_bwd(
+        _pw_dgrad(do, P["pointwise_conv2.weight"]), u, P["depthwise_conv.weight"], P["norm.weight"], P["norm.bias"], B, N,
+        (c, gmean, grstd))
+    G["pointwise_conv1.weight"], G["pointwise_conv1.bias"] = _pw_wgrad(du, t)
+    dx, G["layer_norm.weight"], G["layer_norm.bias"] = _ln_bwd(_pw_dgrad(du, P["pointwise_conv1.weight"]), x, mean, rstd,
+                                                               P["layer_norm.weight"], dres=dy)
+    return dx, G
+
+
+def _padded_tokens(qkv, N):
+    """the unfused route's row length: N as it is where its GEMMs take it (16-byte rows), else the next such length"""
+    a = 8 if qkv.dtype == torch.bfloat16 else 4
+    return (N + a - 1) // a * a
+
+
+def _pad_tokens(x, B, N, Np):
+    xp = torch.zeros(B, Np, x.shape[1], dtype=x.dtype, device=x.device)
+    xp[:, :N] = x.view(B, N, x.shape[1])
+    return xp.view(B * Np, x.shape[1])
+
+
+def plain_attention_fwd(qkv, B, N, h, save=True):
+    """the blocks' attention -> (a [B*N, D], aux): the fused kernel in bfloat16 with N >= 32 (aux = lse), else the unfused
+    GEMM route (aux = P), the parity route; there a token count off the 16-byte row is padded with keys masked by a -1e30
+    score bias (torch copies in and out)"""
+    if _global_fused(qkv, N):
+        return attention_fwd(qkv, B, N, h, save=save)
+    Np = _padded_tokens(qkv, N)
+    if Np == N:
+        return attention_unfused_fwd(qkv, B, N, h)
+    bias = torch.zeros(h, Np, Np, dtype=torch.float32, device=qkv.device)
+    bias[:, :, N:] = -1e30
+    out, P = attention_unfused_fwd(_pad_tokens(qkv, B, N, Np), B, Np, h, bias=bias)
+    return out.view(B, Np, -1)[:, :N].reshape(B * N, -1), P
+
+
+def plain_attention_bwd(qkv, a, da, aux, B, N, h):
+    if _global_fused(qkv, N):
+        return attention_bwd(qkv, a, da, aux, B, N, h)
+    Np = _padded_tokens(qkv, N)
+    if Np == N:
+        return attention_unfused_bwd(qkv, aux, da, B, N, h)
+    dqkv = attention_unfused_bwd(_pad_tokens(qkv, B, N, Np), aux, _pad_tokens(da, B, N, Np), B, Np, h)
+    return dqkv.view(B, Np, -1)[:, :N].reshape(B * N, -1)
+
+
+BLOCK_SAVED = 31      # entries of a block's `saved`
+
+
+def conformer_block_fwd(x, P, B, N, h, eps=1e-5, conv_eps=1e-5, gn_eps=1e-5, squeeze=False, conv_drop=None, save=True):
+    """ConformerBlock (squeeze=False) / SqueezeConformerBlock (squeeze=True) on x [B*N, D]:
+    x + 1/2 ffn1 -> + attention -> + the ConvModule's branch -> (SE gate) -> + 1/2 ffn2 -> final_norm -> (y, saved)"""
+    n1, m1, r1 = layernorm_fwd(x, P["ffn1_norm.weight"], P["ffn1_norm.bias"], eps, save)
+    x1, (pre1,) = silu_ffn_fwd(n1, *[P["ffn1." + n] for n in FFN_NAMES], alpha=0.5, residual=x)
+    n2, m2, r2 = layernorm_fwd(x1, P["attn_norm.weight"], P["attn_norm.bias"], eps, save)
+    qkv = _pw(n2, P["attn.qkv.weight"], bias=P["attn.qkv.bias"])
+    a, aux = plain_attention_fwd(qkv, B, N, h, save)
+    x2 = _pw(a, P["attn.proj.weight"], bias=P["attn.proj.bias"], residual=x1)
+    x3, cs = conv_module_fwd(x2, _sub(P, "conv_module."), B, N, conv_eps, gn_eps, conv_drop, save)
+    x4, ss = x3, (None,) * 4
+    if squeeze:
+        x4, ss = se_fwd(x3, P["se.fc1.weight"], P["se.fc1.bias"], P["se.fc2.weight"], P["se.fc2.bias"], B, N)
+    n5, m5, r5 = layernorm_fwd(x4, P["ffn2_norm.weight"], P["ffn2_norm.bias"], eps, save)
+    x5, (pre2,) = silu_ffn_fwd(n5, *[P["ffn2." + n] for n in FFN_NAMES], alpha=0.5, residual=x4)
+    y, m6, r6 = layernorm_fwd(x5, P["final_norm.weight"], P["final_norm.bias"], eps, save)
+    saved = (n1, m1, r1, pre1, x1, n2, m2, r2, qkv, a, aux, x2) + cs + (x3,) + ss + (n5, m5, r5, pre2, x5, m6, r6)
+    return y, saved
+
+
+def conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=False, conv_drop=None):
+    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32})"""
+    n1, m1, r1, pre1, x1, n2, m2, r2, qkv, a, aux, x2 = saved[:12]
+    cs, x3, ss = saved[12:19], saved[19], saved[20:24]
+    n5, m5, r5, pre2, x5, m6, r6 = saved[24:]
+    G = {}
+    d5, G["final_norm.weight"], G["final_norm.bias"] = _ln_bwd(dy, x5, m6, r6, P["final_norm.weight"])
+    dn5, g = silu_ffn_bwd(d5, n5, P["ffn2.lin1.weight"], P["ffn2.lin2.weight"], (pre2,), 0.5)
+    _put(G, "ffn2.", FFN_NAMES, g)
+    if squeeze:
+        x4 = torch.empty_like(x3)
+        check(lib.htrvt_se_scale_fwd(ptr(x3), ptr(ss[3]), ptr(x4), B, N, x3.shape[1], dt(x3.dtype), stream()), "se_scale_fwd")
+    else:
+        x4 = x3
+    d4, G["ffn2_norm.weight"], G["ffn2_norm.bias"] = _ln_bwd(dn5, x4, m5, r5, P["ffn2_norm.weight"], dres=d5)
+    d3 = d4
+    if squeeze:
+        d3, g = se_bwd(d4, x3, P["se.fc1.weight"], P["se.fc2.weight"], B, N, ss)
+        _put(G, "se.", ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"), g)
+    d2, gc = conv_module_bwd(d3, x2, _sub(P, "conv_module."), cs, B, N, conv_drop)
+    _put(G, "conv_module.", gc.keys(), gc.values())
+    G["attn.proj.weight"], G["attn.proj.bias"] = _pw_wgrad(d2, a)
+    dqkv = plain_attention_bwd(qkv, a, _pw_dgrad(d2, P["attn.proj.weight"]), aux, B, N, h)
+    G["attn.qkv.weight"], G["attn.qkv.bias"] = _pw_wgrad(dqkv, n2)
+    d1, G["attn_norm.weight"], G["attn_norm.bias"] = _ln_bwd(_pw_dgrad(dqkv, P["attn.qkv.weight"]), x1, m2, r2,
+                                                             P["attn_norm.weight"], dres=d2)
+    dn1, g = silu_ffn_bwd(d1, n1, P["ffn1.lin1.weight"], P["ffn1.lin2.weight"], (pre1,), 0.5)
+    _put(G, "ffn1.", FFN_NAMES, g)
+    dx, G["ffn1_norm.weight"], G["ffn1_norm.bias"] = _ln_bwd(dn1, x, m1, r1, P["ffn1_norm.weight"], dres=d1)
+    return dx, G
+
+
+def squeeze_block_fwd(x, P, B, N, h, **kw):
+    return conformer_block_fwd(x, P, B, N, h, squeeze=True, **kw)
+
+
+def squeeze_block_bwd(dy, x, P, saved, B, N, h, conv_drop=None):
+    return conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=True, conv_drop=conv_drop)
+
+
+def squeezeformer_fwd(x, P, B, N0, h, d1, d2, conv_drops=None, save=True, **kw):
+    """SqueezeFormerEncoder on x [B*N0, D]: d1 blocks at N0 tokens, Downsample1D, d2 blocks at N0 // 2, Upsample1D back to N0
+    plus the skip, out_norm -> (y, saved).  conv_drops: per block (stage1 then stage2) None or (seeds, p)"""
+    drops = conv_drops or [None] * (d1 + d2)
+    n = N0 // 2 if N0 > 1 else N0
+    saved = ()
+    for i in range(d1):
+        y, s = squeeze_block_fwd(x, _sub(P, f"stage1.{i}."), B, N0, h, conv_drop=drops[i], save=save, **kw)
+        saved, x = saved + (x,) + s, y
+    skip, x = x, seq_down2_fwd(x, B, N0)
+    for i in range(d2):
+        y, s = squeeze_block_fwd(x, _sub(P, f"stage2.{i}."), B, n, h, conv_drop=drops[d1 + i], save=save, **kw)
+        saved, x = saved + (x,) + s, y
+    z = seq_up_add_fwd(x, skip, B, n, N0)
+    y, mean, rstd = layernorm_fwd(z, P["out_norm.weight"], P["out_norm.bias"], kw.get("eps", 1e-5), save)
+    return y, saved + (z, mean, rstd)
+
+
+def squeezeformer_bwd(dy, P, saved, B, N0, h, d1, d2, conv_drops=None):
+    """dy [B*N0, D] -> (dx, {parameter gradients by the fork's names, float32})"""
+    drops = conv_drops or [None] * (d1 + d2)
+    n = N0 // 2 if N0 > 1 else N0
+    L = BLOCK_SAVED + 1
+    z, mean, rstd = saved[-3:]
+    G = {}
+    dz, G["out_norm.weight"], G["out_norm.bias"] = _ln_bwd(dy, z, mean, rstd, P["out_norm.weight"])
+    d = seq_up_add_bwd(dz, B, n, N0)
+    for i in reversed(range(d2)):
+        blk = saved[(d1 + i) * L:(d1 + i + 1) * L]
+        d, g = squeeze_block_bwd(d, blk[0], _sub(P, f"stage2.{i}."), blk[1:], B, n, h, drops[d1 + i])
+        _put(G, f"stage2.{i}.", g.keys(), g.values())
+    d = convert(seq_down2_bwd(d, B, N0), dz.clone(), accumulate=True) if N0 > 1 else d + dz
+    for i in reversed(range(d1)):
+        blk = saved[i * L:(i + 1) * L]
+        d, g = squeeze_block_bwd(d, blk[0], _sub(P, f"stage1.{i}."), blk[1:], B, N0, h, drops[i])
+        _put(G, f"stage1.{i}.", g.keys(), g.values())
+    return d, G

@@ -538,3 +538,108 @@ def neighborhood_attention_2d(qkv, B, H, W, heads, kernel=(7, 11)):
     if len(kernel) != 2 or not nbr2d_supported(qkv.shape[1] // 3 // heads, kernel, qkv.dtype):
         raise ValueError(f"neighbourhood attention: {lib.htrvt_last_error().decode()}")
     return _NeighborhoodAttention2D.apply(qkv, B, H, W, heads, kernel)
+
+
+# ---- convolutional forks (model_sgm_mms_conv*/model/HTR_VT.py ConvModule, SqueezeExcite1D, Downsample1D, Upsample1D): csrc/gnmixer.hip
+
+def _f32_params(name, *params):
+    if any(t.dtype != torch.float32 for t in params):
+        raise TypeError(f"{name}: float32 parameters expected (as stored)")
+
+
+class _GluDwconvGnSilu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, weight, bias, gn_weight, gn_bias, B, N, eps):
+        u, weight, bias, gn_weight, gn_bias = [t.contiguous() for t in (u, weight, bias, gn_weight, gn_bias)]
+        s, saved = seq_ops.gn_mixer_fwd(u, weight, bias, gn_weight, gn_bias, B, N, eps)
+        ctx.save_for_backward(u, weight, gn_weight, gn_bias, *saved)
+        ctx.dims = (B, N)
+        return s
+
+    @staticmethod
+    def backward(ctx, ds):
+        u, weight, gamma, beta, *saved = ctx.saved_tensors
+        grads = seq_ops.gn_mixer_bwd(ds.contiguous().to(u.dtype), u, weight, gamma, beta, *ctx.dims, saved)
+        return grads + (None,) * 3
+
+
+def glu_dwconv_gn_silu(u, weight, bias, gn_weight, gn_bias, B, N, eps=1e-5):
+    """ConvModule between its 1x1 convolutions: u [B*N, 2*C] (float32 or bfloat16) -> silu(GroupNorm(1, C)(dwconv(glu(u)) +
+    bias)) [B*N, C].  weight: depthwise_conv.weight float32 [C, 1, k], k odd <= 15, zero padding per image; bias, gn_weight,
+    gn_bias float32 [C].  The statistics are per image over its C * N values, in train and eval mode alike.  C a multiple of
+    8 (bfloat16) or 4.  Differentiable in all five tensors; the gradients are bitwise reproducible."""
+    _need_device(u, weight, bias, gn_weight, gn_bias)
+    _f32_params("glu_dwconv_gn_silu", weight, bias, gn_weight, gn_bias)
+    if u.dim() != 2 or u.shape[0] != B * N or weight.dim() != 3 or u.shape[1] != 2 * weight.shape[0] or weight.shape[1] != 1:
+        raise ValueError(f"glu_dwconv_gn_silu: u [B*N, 2*C] and weight [C, 1, k] expected, got {tuple(u.shape)} and "
+                         f"{tuple(weight.shape)}")
+    return _GluDwconvGnSilu.apply(u, weight, bias, gn_weight, gn_bias, B, N, float(eps))
+
+
+class _SqueezeExcite(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, B, N):
+        x, w1, b1, w2, b2 = [t.contiguous() for t in (x, w1, b1, w2, b2)]
+        y, saved = seq_ops.se_fwd(x, w1, b1, w2, b2, B, N)
+        ctx.save_for_backward(x, w1, w2, *saved)
+        ctx.dims = (B, N)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, *saved = ctx.saved_tensors
+        dx, g = seq_ops.se_bwd(dy.contiguous().to(x.dtype), x, w1, w2, *ctx.dims, saved)
+        return (dx,) + g + (None, None)
+
+
+def squeeze_excite(x, fc1_w, fc1_b, fc2_w, fc2_b, B, N):
+    """SqueezeExcite1D on x [B*N, D] (float32 or bfloat16): x * sigmoid(fc2(silu(fc1(mean over the N tokens of the image)))).
+    fc1_w [H, D], fc1_b [H], fc2_w [D, H], fc2_b [D] float32; the MLP runs in float32.  Differentiable in all five."""
+    _need_device(x, fc1_w, fc1_b, fc2_w, fc2_b)
+    _f32_params("squeeze_excite", fc1_w, fc1_b, fc2_w, fc2_b)
+    if x.dim() != 2 or x.shape[0] != B * N or fc1_w.shape[1] != x.shape[1] or tuple(fc2_w.shape) != tuple(fc1_w.shape)[::-1]:
+        raise ValueError(f"squeeze_excite: x [B*N, D], fc1_w [H, D], fc2_w [D, H] expected, got {tuple(x.shape)}, "
+                         f"{tuple(fc1_w.shape)}, {tuple(fc2_w.shape)}")
+    return _SqueezeExcite.apply(x, fc1_w, fc1_b, fc2_w, fc2_b, B, N)
+
+
+class _SeqDownsample2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, B, N):
+        ctx.dims = (B, N)
+        return seq_ops.seq_down2_fwd(x.contiguous(), B, N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return seq_ops.seq_down2_bwd(dy.contiguous(), *ctx.dims), None, None
+
+
+def seq_downsample2(x, B, N):
+    """Downsample1D on x [B*N, D]: avg_pool1d(2, 2) along the tokens -> [B*(N // 2), D]; N <= 1 is the identity"""
+    _need_device(x)
+    if x.dim() != 2 or x.shape[0] != B * N:
+        raise ValueError(f"seq_downsample2: x [B*N, D] expected, got {tuple(x.shape)}")
+    return x if N <= 1 else _SeqDownsample2.apply(x, B, N)
+
+
+class _SeqUpsampleAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, skip, B, n, N0):
+        ctx.dims = (B, n, N0)
+        return seq_ops.seq_up_add_fwd(y.contiguous(), skip.contiguous(), B, n, N0)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        return seq_ops.seq_up_add_bwd(dout, *ctx.dims), dout, None, None, None
+
+
+def seq_upsample_add(y, skip, B, n, N0):
+    """Upsample1D fused with the skip add: y [B*n, D], skip [B*N0, D] -> skip + y at token (i * n) // N0, F.interpolate's
+    nearest index"""
+    _need_device(y, skip)
+    if y.dim() != 2 or skip.dim() != 2 or y.shape[0] != B * n or skip.shape[0] != B * N0 or y.shape[1] != skip.shape[1] \
+            or y.dtype != skip.dtype or not 1 <= n <= N0:
+        raise ValueError(f"seq_upsample_add: y [B*n, D] and skip [B*N0, D] of one dtype expected, got {tuple(y.shape)} and "
+                         f"{tuple(skip.shape)}")
+    return _SeqUpsampleAdd.apply(y, skip, B, n, N0)

@@ -645,6 +645,74 @@ int htrvt_mixer_bwd(const void* u, const void* c, const void* ds, const float* w
                     const float* coef, void* du, float* dw_partial, float* db_partial, int B, int N, int D, int k, int dtype,
                     void* stream);
 
+/* ---- the convolutional forks' blocks (model_sgm_mms_conv/model/HTR_VT.py:103-166 FeedForward and ConvModule;
+ * model_sgm_mms_conv_squeeze/model/HTR_VT.py:169-223 SqueezeExcite1D, Downsample1D, Upsample1D): csrc/gnmixer.hip.
+ * Token rows as the GEMMs leave them; activations of type dtype (float32 or bfloat16), 16-byte aligned, their channel count a
+ * multiple of the 16-byte vector (8 bfloat16, 4 float32); statistics, parameters and parameter gradients float32; offsets
+ * 64-bit.  Every sum is formed in a fixed order (no float atomics): two runs give the same bits.  Refused (negative return,
+ * htrvt_last_error(), nothing launched): another dtype, a channel count off the vector, misaligned buffers, k even or outside
+ * 1 ... 15, a shape whose grid does not fit one launch.
+ *
+ * GroupNorm mixer, ConvModule between its two 1x1 convolutions: u [B*N][2C] (pointwise_conv1's output: value half, gate half)
+ *   g = u[:, :C] * sigmoid(u[:, C:]),  c[b][n][d] = bias[d] + sum_j w[d][j] * g[b][n + j - k/2][d]  (zero padding per image),
+ *   z = (c - mean_b) * rstd_b * gamma + beta,  s = z * sigmoid(z),
+ * mean_b and rstd_b = 1 / sqrt(var_b + eps) over ALL C * N values of image b (nn.GroupNorm(1, C), biased variance), taken
+ * from c as stored (rounded to dtype).  Train and eval are the same computation.  w float32 [C][k], bias / gamma / beta [C]
+ * (NULL: 0 / 1 / 0).  A workgroup's runs all lie in one image, so every partial belongs to one image:
+ *   htrvt_gnmixer_rows(B, N, C, dtype)   R: workgroup rows of the launches (rows of the per-channel and dw / db partials)
+ *   htrvt_gnmixer_parts(B, N, C, dtype)  P: partial pairs per image; pairs is float32 [B][P][2]
+ * Forward: htrvt_gnmixer_fwd (c, pairs = (sum c, sum c^2)) -> htrvt_gn_finalize(pairs, B, P, count = C * N, eps) (mean [B],
+ *   rstd [B]; the pairs added in order in float64) -> htrvt_gnmixer_act (s; also the backward's way back to s).
+ * Backward, dz = ds * silu'(z), xhat = (c - mean_b) * rstd_b:
+ *   htrvt_gnmixer_bwd_reduce -> chan_partial [R][2][C] = (sum dz, sum dz * xhat) per channel, whose column sums (htrvt_colsum
+ *     over 2 C columns) are (d beta | d gamma), and pairs [B][P][2] = (sum gamma dz, sum gamma dz xhat) per image;
+ *   htrvt_gn_bwd_finalize(pairs, B, P, count = C * N) -> m1 [B], m2 [B], the two means;
+ *   htrvt_gnmixer_bwd: dc = rstd_b * (gamma dz - m1_b - xhat * m2_b) on the fly, dg = dc convolved with the flipped taps, du
+ *     [B*N][2C] through the GLU recomputed from u; dw_partial [R][C * k] and db_partial [R][C] (db = sum dc), summed by
+ *     htrvt_colsum. */
+int htrvt_gnmixer_rows(int B, int N, int C, int dtype);
+int htrvt_gnmixer_parts(int B, int N, int C, int dtype);
+int htrvt_gnmixer_fwd(const void* u, const float* w, const float* bias, void* c, float* pairs, int B, int N, int C, int k,
+                      int dtype, void* stream);
+int htrvt_gn_finalize(const float* pairs, int B, int P, double count, float eps, float* mean, float* rstd, void* stream);
+int htrvt_gnmixer_act(const void* c, const float* mean, const float* rstd, const float* gamma, const float* beta, void* s,
+                      int B, int N, int C, int dtype, void* stream);
+int htrvt_gnmixer_bwd_reduce(const void* ds, const void* c, const float* mean, const float* rstd, const float* gamma,
+                             const float* beta, float* chan_partial, float* pairs, int B, int N, int C, int dtype,
+                             void* stream);
+int htrvt_gn_bwd_finalize(const float* pairs, int B, int P, double count, float* m1, float* m2, void* stream);
+int htrvt_gnmixer_bwd(const void* u, const void* c, const void* ds, const float* w, const float* mean, const float* rstd,
+                      const float* gamma, const float* beta, const float* m1, const float* m2, void* du, float* dw_partial,
+                      float* db_partial, int B, int N, int C, int k, int dtype, void* stream);
+/* Squeeze-excite gate on x [B*N][D]: y = x * g[b], g = sigmoid(fc2(silu(fc1(mean over the tokens)))), all of the MLP float32.
+ * Forward: htrvt_se_mean (mean [B][D]) -> htrvt_se_mlp_fwd (one workgroup per image; fc1 w1 [H][D], b1 [H], fc2 w2 [D][H],
+ *   b2 [D]; pre [B][H] = fc1's output, act = silu(pre), g [B][D]) -> htrvt_se_scale_fwd (y).
+ * Backward: htrvt_se_scale_bwd_reduce (dg[b][d] = sum_n dy * x) -> htrvt_se_mlp_bwd (dh2 [B][D], dh1 [B][H]: the gradients at
+ *   fc2's and fc1's outputs; dmean [B][D]) -> htrvt_se_wgrad twice (dW [M][K] = sum_b dy[b][m] x[b][k], db [M] = sum_b dy[b][m],
+ *   b in increasing order: (dh2, act) for fc2, (dh1, mean) for fc1) -> htrvt_se_scale_bwd (dx = dy * g[b] + dmean[b] / N). */
+int htrvt_se_mean(const void* x, float* mean, int B, int N, int D, int dtype, void* stream);
+int htrvt_se_mlp_fwd(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, float* pre,
+                     float* act, float* g, int B, int D, int H, void* stream);
+int htrvt_se_scale_fwd(const void* x, const float* g, void* y, int B, int N, int D, int dtype, void* stream);
+int htrvt_se_scale_bwd_reduce(const void* dy, const void* x, float* dg, int B, int N, int D, int dtype, void* stream);
+int htrvt_se_mlp_bwd(const float* dg, const float* g, const float* pre, const float* w1, const float* w2, float* dh2, float* dh1,
+                     float* dmean, int B, int D, int H, void* stream);
+int htrvt_se_wgrad(const float* dy, const float* x, float* dw, float* db, int B, int M, int K, void* stream);
+int htrvt_se_scale_bwd(const void* dy, const float* g, const float* dmean, void* dx, int B, int N, int D, int dtype,
+                       void* stream);
+/* Resampling of token rows.  down2: y[b][j] = (x[b][2j] + x[b][2j+1]) / 2, j < N / 2 (avg_pool1d(2, 2): an odd last token is
+ * dropped and gets a zero gradient); N >= 2 (N <= 1 is the identity, the caller's).  up_add: out[b][i] = y[b][(i * n) / N0] +
+ * skip[b][i], i < N0, 1 <= n <= N0: nearest up-sampling (F.interpolate's index) fused with the skip add; its backward sums the
+ * targets of each source token in increasing order, and the skip's gradient is dout itself. */
+int htrvt_seq_down2_fwd(const void* x, void* y, int B, int N, int D, int dtype, void* stream);
+int htrvt_seq_down2_bwd(const void* dy, void* dx, int B, int N, int D, int dtype, void* stream);
+int htrvt_seq_up_add_fwd(const void* y, const void* skip, void* out, int B, int n, int N0, int D, int dtype, void* stream);
+int htrvt_seq_up_add_bwd(const void* dout, void* dy, int B, int n, int N0, int D, int dtype, void* stream);
+/* FeedForward's activation between its two GEMMs (htrvt_gemm's epilogues are GELU only): a = silu(pre), dpre = da * silu'(pre),
+ * n elements, a multiple of the vector */
+int htrvt_silu_fwd(const void* pre, void* a, int64_t n, int dtype, void* stream);
+int htrvt_silu_bwd(const void* da, const void* pre, void* dpre, int64_t n, int dtype, void* stream);
+
 /* The VAN forks' height reducer and horizontal mixer (model_sgm_mms_attach_van/model/HTR_VT.py:159-254 LargeKernelAttention,
  * VANBlock, VANHeightReducer, HorizontalMixer; model_sgm_mms_attach_van_2 is identical): what they need beside the 1x1
  * convolutions (htrvt_gemm on the [B*H*W][C] rows) and the BatchNorm passes (htrvt_bn_*), csrc/van.hip.
