@@ -7,48 +7,11 @@ import ctypes
 import pytest
 import torch
 
+from attn_refs import windowed_reference as _reference
+
 pytestmark = pytest.mark.gpu
 
 CASES = [(N, hd, ws, shift) for N in (64, 128, 200, 256) for hd in (64, 128) for ws, shift in ((0, 0), (16, 0), (16, 8))]
-
-
-def _reference(qkv, table, B, N, h, hd, P, ws, shift):
-    """float64, the reference's own sequence of operations on the per-token q/k/v (the qkv Linear commutes with the pad,
-    roll and partition, which only move whole tokens; padding tokens are masked as keys and dropped as queries)"""
-    D = h * hd
-    x = qkv.double().reshape(B, N, 3 * D)
-    table = table.double()
-
-    def attn(xw, valid=None):                          # Attention.forward on [B', n, 3D]
-        Bp, n, _ = xw.shape
-        q, k, v = xw.reshape(Bp, n, 3, h, hd).permute(2, 0, 3, 1, 4).unbind(0)
-        a = (q @ k.transpose(-2, -1)) * hd ** -0.5
-        coords = torch.arange(P)
-        idx = (coords[None, :] - coords[:, None]) + P - 1
-        a = a + table[idx[:n, :n]].permute(2, 0, 1).unsqueeze(0)
-        if valid is not None:
-            a = a.masked_fill(~valid.reshape(Bp, 1, 1, n), torch.finfo(a.dtype).min)
-        a = a.softmax(-1)
-        if valid is not None:
-            a = torch.nan_to_num(a, nan=0.0)
-        return (a @ v).transpose(1, 2).reshape(Bp, n, D)
-
-    if ws <= 0:
-        return attn(x).reshape(B * N, D)
-    pad = (ws - N % ws) % ws
-    if pad:
-        x = torch.cat([x, torch.zeros(B, pad, 3 * D, dtype=x.dtype)], dim=1)
-    Np = x.shape[1]
-    valid = torch.ones(B, Np, dtype=torch.bool)
-    if pad:
-        valid[:, -pad:] = False
-    if shift > 0:
-        x = torch.roll(x, shifts=(-shift,), dims=1)
-        valid = torch.roll(valid, shifts=(-shift,), dims=1)
-    y = attn(x.reshape(B * (Np // ws), ws, 3 * D), valid.reshape(B * (Np // ws), ws)).reshape(B, Np, D)
-    if shift > 0:
-        y = torch.roll(y, shifts=(shift,), dims=1)
-    return y[:, :N].reshape(B * N, D)
 
 
 def _inputs(B, N, h, hd, P, seed):
