@@ -28,7 +28,9 @@ project's gate, 2e-3 absolute, per element.
 
 Constructions with exact expectations: one_hot_case, uniform_window_case, window1_case (each says why it is exact).
 windowed_reference is the float64 restatement of the window fork that tests/test_attn_relpos_gpu.py uses (moved here, not
-forked).  guarded() / assert_guards_intact() put device outputs between two bands of a fixed bit pattern."""
+forked).  guarded() / assert_guards_intact() put device outputs between two bands of a fixed bit pattern.
+tests/window_refs.py builds the references of the VALU window / box attention kernels on attention_f64 (its dtype and
+delta_from_p arguments serve that file); their per-element gates live in tests/test_window_edges_gpu.py."""
 import functools
 import math
 from types import SimpleNamespace
@@ -73,9 +75,9 @@ def one_hot_grid(N):
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------
-def split_heads(x, B, N, h, hd, parts=3):
+def split_heads(x, B, N, h, hd, parts=3, dtype=torch.float64):
     """[B*N, parts*h*hd] -> parts tensors [B, h, N, hd] (float64)"""
-    y = x.double().reshape(B, N, parts, h, hd).permute(2, 0, 3, 1, 4)
+    y = x.to(dtype).reshape(B, N, parts, h, hd).permute(2, 0, 3, 1, 4)
     return [y[i] for i in range(parts)]
 
 
@@ -91,28 +93,31 @@ def bf16(x):
 
 
 # ---- float64 reference ----------------------------------------------------------------------------------------------
-def attention_f64(qkv, B, N, h, hd, bias=None, dout=None):
+def attention_f64(qkv, B, N, h, hd, bias=None, dout=None, dtype=torch.float64, delta_from_p=False):
     """softmax(q k^T hd^-0.5 + bias) v in float64, operands as given.  bias: [h, N, N] or None, -inf allowed (every query
-    must keep a key).  -> namespace: O [B*N, h*hd], lse2 [B, h, N] (base-2 log of the softmax denominator), the
-    per-head q / k / v / P [B, h, N, .]; with dout also dQ / dK / dV [B*N, h*hd], delta [B, h, N], dP and
-    dscore = P (dP - delta) [B, h, N, N] (gradient of the score behind the scale: of a bias entry), do."""
-    q, k, v = split_heads(qkv, B, N, h, hd)
+    must keep a key).  -> namespace: O [B*N, h*hd], lse2 [B, h, N] (base-2 log of the softmax denominator; lse: the natural
+    one), the per-head q / k / v / P [B, h, N, .]; with dout also dQ / dK / dV [B*N, h*hd], delta [B, h, N], dP and
+    dscore = P (dP - delta) [B, h, N, N] (gradient of the score behind the scale: of a bias entry), do.
+    dtype: the type everything is evaluated in (torch.float32: the same operation in float32, for kernel_refs.e32).
+    delta_from_p: delta = sum_k P dP, the same number formed the way the recomputing window kernels form it (a query with
+    a single key then has dscore exactly 0)."""
+    q, k, v = split_heads(qkv, B, N, h, hd, dtype=dtype)
     scale = hd ** -0.5
     s = (q @ k.transpose(-1, -2)) * scale
     if bias is not None:
-        s = s + bias.double().unsqueeze(0)
+        s = s + bias.to(dtype).unsqueeze(0)
     m = s.max(-1, keepdim=True).values
     e = torch.exp(s - m)
     l = e.sum(-1, keepdim=True)
     P = e / l
     o = P @ v
     r = SimpleNamespace(B=B, N=N, h=h, hd=hd, scale=scale, q=q, k=k, v=v, P=P, o=o, O=merge_heads(o),
-                        lse2=((m + torch.log(l)) * LOG2E).squeeze(-1))
+                        lse2=((m + torch.log(l)) * LOG2E).squeeze(-1), lse=(m + torch.log(l)).squeeze(-1))
     if dout is None:
         return r
-    do = split_heads(dout, B, N, h, hd, parts=1)[0]
+    do = split_heads(dout, B, N, h, hd, parts=1, dtype=dtype)[0]
     dP = do @ v.transpose(-1, -2)
-    delta = (do * o).sum(-1)
+    delta = (P * dP).sum(-1) if delta_from_p else (do * o).sum(-1)
     dscore = P * (dP - delta.unsqueeze(-1))
     dS = dscore * scale
     r.do, r.dP, r.delta, r.dscore = do, dP, delta, dscore

@@ -4,12 +4,16 @@ against float64 torch restatements of model_lgp/model/plg.py on the same (for bf
 Gates (those of tests/test_attn_relpos_gpu.py, the kernels these sit beside): bfloat16 forward max-abs < 2.5e-2, gradients
 3e-2 of the tensor's maximum with cosine > 0.9995; float32 window attention forward max-abs < 2e-5, gradients 1e-4 of the
 maximum with cosine > 0.999999.  Pooling + LayerNorm and up-sampling in float32, forward and backward, d logit_alpha
-included: 1e-5 of the output's maximum (of the value, for the scalar)."""
+included: 1e-5 of the output's maximum (of the value, for the scalar).  These are gates on a whole tensor; the per-element
+gates of the window attention kernels live in tests/test_window_edges_gpu.py (references and error model:
+tests/window_refs.py, proved on the host by tests/test_window_refs_cpu.py)."""
 import ctypes
 
 import pytest
 import torch
 import torch.nn.functional as F
+
+from window_refs import ref_local
 
 pytestmark = pytest.mark.gpu
 
@@ -35,18 +39,7 @@ def _rounded(t, dtype):
 
 
 # ---------------------------------------------------------------------------------------------- window attention
-def _ref_local(qkv, bias, B, N, h, hd, w):
-    """WindowMHSA1D.forward (plg.py:109-137) on the qkv Linear's output: a zero padding token leaves the Linear as its bias"""
-    D = h * hd
-    x = qkv.reshape(B, N, 3 * D)
-    pad = (w - N % w) % w
-    if pad:
-        x = torch.cat([x, bias.reshape(1, 1, 3 * D).expand(B, pad, 3 * D)], dim=1)
-    Np = N + pad
-    q, k, v = x.reshape(B * (Np // w), w, 3, h, hd).permute(2, 0, 3, 1, 4).unbind(0)
-    a = ((q @ k.transpose(-2, -1)) * hd ** -0.5).softmax(dim=-1)
-    out = (a @ v).transpose(1, 2).reshape(B, Np, D)
-    return out[:, :N].reshape(B * N, D)
+_ref_local = ref_local            # WindowMHSA1D.forward restated in float64: tests/window_refs.py holds it now
 
 
 def _local_inputs(B, N, h, hd, dtype, seed):

@@ -4,42 +4,22 @@ Linear's output: roll by `shift`, pad with rows equal to the bias (what the Line
 windows, crop, roll back.  Same (for bfloat16: bfloat16-rounded) unit-scale inputs on both sides.
 
 Gates: `_gate` / `_grad_gate` of tests/test_lgp_kernels_gpu.py, the unshifted kernel's (float32 1e-4 of the maximum with
-cosine > 0.999999, bfloat16 3e-2 with cosine > 0.9995), and its forward max-abs bounds (2e-5 / 2.5e-2)."""
+cosine > 0.999999, bfloat16 3e-2 with cosine > 0.9995), and its forward max-abs bounds (2e-5 / 2.5e-2).  The per-element
+gates of these kernels (wrap and padding rows in one window, every window size) live in tests/test_window_edges_gpu.py."""
 import ctypes
 
 import pytest
 import torch
 
 from test_lgp_kernels_gpu import DTYPES, _gate, _grad_gate, _local_inputs
+from window_refs import ref_shifted
 
 pytestmark = pytest.mark.gpu
 
 B, HEADS = 2, 2
 
 
-def _ref_shifted(qkv, bias, B, N, h, hd, w, s, mask_wrap=False):
-    """[B*N, 3D] float64 -> [B*N, D]; mask_wrap: the Swin-style mask the fork does NOT have (no attention between the tokens
-    rolled in from the end of the line and the ones from its start)"""
-    D = h * hd
-    x = qkv.reshape(B, N, 3 * D)
-    s = s % w
-    if s:
-        x = torch.roll(x, shifts=s, dims=1)
-    pad = (w - N % w) % w
-    if pad:
-        x = torch.cat([x, bias.reshape(1, 1, 3 * D).expand(B, pad, 3 * D)], dim=1)
-    Np = N + pad
-    nW = Np // w
-    q, k, v = x.reshape(B * nW, w, 3, h, hd).permute(2, 0, 3, 1, 4).unbind(0)
-    sc = (q @ k.transpose(-2, -1)) * hd ** -0.5                      # [B nW, h, w, w]
-    if mask_wrap:
-        side = (torch.arange(Np) < (s % N)).reshape(nW, w)            # slots holding tokens from the end of the line
-        cross = (side[:, :, None] != side[:, None, :]).repeat(B, 1, 1)[:, None]
-        sc = sc.masked_fill(cross, float("-inf"))
-    out = (sc.softmax(dim=-1) @ v).transpose(1, 2).reshape(B, Np, D)[:, :N]
-    if s:
-        out = torch.roll(out, shifts=-s, dims=1)
-    return out.reshape(B * N, D)
+_ref_shifted = ref_shifted        # the shifted WindowMHSA1D.forward restated in float64: tests/window_refs.py holds it now
 
 
 def _run(qkv, bias, dout, N, h, w, s, dtype):

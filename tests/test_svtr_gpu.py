@@ -5,7 +5,8 @@ modules in float64).
 Kernel gates are the project's for window attention (tests/test_swin_gpu.py), against the float64 reference over the same
 (already rounded) inputs: forward max-abs < 2.5e-2 (bfloat16) / 2e-5 (float32); dqkv within 3e-2 / 1e-4 of the tensor's
 largest magnitude, cosine > 0.9995 / 0.999999.  Every output buffer (out, lse, dqkv) carries one canary row behind it that
-must stay untouched.  Module gates are the project's, relative to the largest reference magnitude per tensor: float32 outputs
+must stay untouched.  (These are gates on a whole tensor.  The per-element gates of the kernels, with guard bands on both sides
+of every output, live in tests/test_window_edges_gpu.py.)  Module gates are the project's, relative to the largest reference magnitude per tensor: float32 outputs
 1e-3, gradients 2e-3; bfloat16 5e-2 and 1e-1.  Every parameter gradient is compared element by element with
 svtr_refs.case_grads over the modules' own state_dicts, which tests/test_svtr_cpu.py anchors to the fork at 1e-10; the output
 and the input gradient also with the fixture itself.  Every comparison prints what it observed (`pytest -s`).
