@@ -136,14 +136,14 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 //   erfc(|x| / sqrt 2) = exp2(a * R(a)),  a = min(|x|, 4 sqrt 2),  R of degree 5 (weighted least squares on Chebyshev nodes,
 //   tools/fit_gelu.py): |erf error| < 3.5e-7 in float32, no reciprocal, ONE v_exp_f32 (libm's erff branches; the former
 //   Abramowitz-Stegun form took a v_rcp_f32 and a v_exp_f32, quarter-rate each).
-//   gelu(x)  = x Phi(x)  = 0.5 x + 0.5 |x| (1 - e)
+//   gelu(x)  = x Phi(x)  = 0.5 x + 0.5 |x| - 0.5 a e
 //   gelu'(x) = Phi(x) + x pdf(x) = 0.5 + copysign(0.5 - 0.5 e, x) + x / sqrt(2 pi) * exp2(-x^2 log2(e) / 2)
 // Measured against float64 over [-12, 12] and N(0, 4) samples: |gelu error| < 5.2e-7, |gelu' error| < 2.7e-7.
 __device__ __forceinline__ f32x2_t splat2(float c) { return f32x2_t{c, c}; }
-__device__ __forceinline__ f32x2_t erfc_abs2(f32x2_t ax) {
-  f32x2_t a;
-  a.x = __builtin_amdgcn_fmed3f(ax.x, 0.f, 5.656854249f);
-  a.y = __builtin_amdgcn_fmed3f(ax.y, 0.f, 5.656854249f);
+__device__ __forceinline__ f32x2_t clamp_abs2(f32x2_t ax) {   // a = min(|x|, 4 sqrt 2)
+  return f32x2_t{__builtin_amdgcn_fmed3f(ax.x, 0.f, 5.656854249f), __builtin_amdgcn_fmed3f(ax.y, 0.f, 5.656854249f)};
+}
+__device__ __forceinline__ f32x2_t erfc_clamped2(f32x2_t a) {   // erfc(a / sqrt 2) of a = clamp_abs2(|x|)
   f32x2_t r = __builtin_elementwise_fma(splat2(1.986000183e-05f), a, splat2(-6.623090474e-04f));
   r = __builtin_elementwise_fma(r, a, splat2(7.759703627e-03f));
   r = __builtin_elementwise_fma(r, a, splat2(-5.296444113e-02f));
@@ -152,15 +152,18 @@ __device__ __forceinline__ f32x2_t erfc_abs2(f32x2_t ax) {
   const f32x2_t t = a * r;
   return f32x2_t{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
 }
+// The tail term is 0.5 a (1 - e) with the CLAMPED a, the magnitude e belongs to: with 0.5 |x| e instead, e = erfc(4) = 1.5e-8
+// stopped falling at |x| = 4 sqrt 2 while |x| went on, and gelu(x) for x < -67 came out as -7.7e-9 |x| instead of 0 (-7.7e-7
+// at -100, -2.6e30 at the largest bfloat16; the bfloat16 sweep of tests/test_gemm_epilogue_gpu.py).  Same bits for |x| <= 4 sqrt 2.
 __device__ __forceinline__ f32x2_t gelu_erf_fast2(f32x2_t x) {
   const f32x2_t ax = __builtin_elementwise_abs(x);
-  const f32x2_t e = erfc_abs2(ax);
-  const f32x2_t h = ax * splat2(0.5f);
-  const f32x2_t m = __builtin_elementwise_fma(x, splat2(0.5f), h);
-  return __builtin_elementwise_fma(-h, e, m);
+  const f32x2_t a = clamp_abs2(ax);
+  const f32x2_t e = erfc_clamped2(a);
+  const f32x2_t m = __builtin_elementwise_fma(x, splat2(0.5f), ax * splat2(0.5f));
+  return __builtin_elementwise_fma(a * splat2(-0.5f), e, m);
 }
 __device__ __forceinline__ f32x2_t gelu_erf_grad_fast2(f32x2_t x) {
-  const f32x2_t e = erfc_abs2(__builtin_elementwise_abs(x));
+  const f32x2_t e = erfc_clamped2(clamp_abs2(__builtin_elementwise_abs(x)));
   const f32x2_t d = __builtin_elementwise_copysign(__builtin_elementwise_fma(e, splat2(-0.5f), splat2(0.5f)), x);
   const f32x2_t q = (x * x) * splat2(-0.72134752044448170368f);
   const f32x2_t pdf = {__builtin_amdgcn_exp2f(q.x), __builtin_amdgcn_exp2f(q.y)};
