@@ -72,6 +72,9 @@ PROTOTYPES = {
     "htrvt_bn_apply_mask": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "htrvt_bn_relu_maxpool": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_pool_tokens": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_pool_tokens_ps": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_mask_tokens_fwd": (i32, [vp, vp, i64, vp, vp, i64, i32, i32, vp]),
+    "htrvt_mask_tokens_bwd": (i32, [vp, vp, i64, vp, i64, i32, i32, vp]),
     "htrvt_layernorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
     "htrvt_softmax_rows": (i32, [vp, vp, i64, i32, i32, vp, i64, vp]),
     "htrvt_attn_supported": (i32, [i32, i32, i32]),
@@ -92,6 +95,7 @@ PROTOTYPES = {
     "htrvt_bn_bwd_apply2": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "htrvt_maxpool_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_pool_tokens_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "htrvt_pool_tokens_bwd_ps": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "htrvt_conv1_bwd_rows": (i32, [i32, i32]),
     "htrvt_conv1_bwd_row_floats": (i32, [i32]),
     "htrvt_conv1_bwd": (i32, [vp] * 12 + [i32, i32, i32, i32, i32, i32, vp]),

@@ -505,8 +505,8 @@ __global__ __launch_bounds__(NT) void maxpool_bwd_kernel(const T* __restrict__ d
 // ------------------------------------------------------------------ token assembly backward (final max-pool)
 template <typename T>
 __global__ __launch_bounds__(NT) void pool_tokens_bwd_kernel(const T* __restrict__ dtok, const T* __restrict__ x,
-                                                             const float* __restrict__ keep, T* __restrict__ dx, int B,
-                                                             int H, int W, int D) {
+                                                             const float* __restrict__ keep, int keep_ld,
+                                                             T* __restrict__ dx, int B, int H, int W, int D) {
   constexpr int CH = Vec16<T>::N;
   const int cvec = D / CH, Ho = (H - 1) / 2 + 1;
   const long long total = (long long)B * H * W * cvec;
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(NT) void pool_tokens_bwd_kernel(const T* __restrict
         const int wo = wi + 1 - dx_;
         if (wo < 0 || wo >= W) continue;
         const int n = ho * W + wo;
-        if (keep != nullptr && keep[n] == 0.f) continue;
+        if (keep != nullptr && keep[(long long)b * keep_ld + n] == 0.f) continue;   // keep_ld 0: one [N] mask
         // first maximum of window (ho,wo) in scan order
         float m[CH];
         int am[CH];
@@ -574,8 +574,8 @@ __global__ __launch_bounds__(NT) void pool_tokens_bwd_kernel(const T* __restrict
 // gradients -- 13 loads per two outputs instead of 42 (the general kernel re-derives every window per input element).
 template <typename T>
 __global__ __launch_bounds__(NT) void pool_tokens_bwd_h2_kernel(const T* __restrict__ dtok, const T* __restrict__ x,
-                                                                const float* __restrict__ keep, T* __restrict__ dx, int B,
-                                                                int W, int D) {
+                                                                const float* __restrict__ keep, int keep_ld,
+                                                                T* __restrict__ dx, int B, int W, int D) {
   constexpr int CH = Vec16<T>::N;
   using Raw = decltype(Vec16<T>().raw);
   const int cvec = D / CH;
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(NT) void pool_tokens_bwd_h2_kernel(const T* __restr
 #pragma unroll
   for (int k = 0; k < 3; ++k) {   // window centred on column wo = wi - 1 + k
     const int wo = wi - 1 + k, woc = min(max(wo, 0), W - 1);
-    live[k] = wo >= 0 && wo < W && (keep == nullptr || keep[woc] != 0.f);
+    live[k] = wo >= 0 && wo < W && (keep == nullptr || keep[(long long)b * keep_ld + woc] != 0.f);
     g[k].raw = dr[(long long)woc * cvec];
   }
   float acc[2][CH];
@@ -943,8 +943,8 @@ extern "C" int htrvt_maxpool_bwd(const void* dpool, const uint8_t* idx, const vo
   return check_launch("maxpool_bwd");
 }
 
-extern "C" int htrvt_pool_tokens_bwd(const void* dtok, const void* x, const float* keep, void* dx, int B, int H, int N,
-                                     int D, int dtype, void* stream) {
+static int pool_tokens_bwd_launch(const void* dtok, const void* x, const float* keep, int keep_ld, void* dx, int B, int H,
+                                  int N, int D, int dtype, void* stream) {
   const int ch = dtype == HTRVT_BF16 ? 8 : 4;
   const int Ho = (H - 1) / 2 + 1;
   HTRVT_REQUIRE(D % ch == 0 && N % Ho == 0, "htrvt_pool_tokens_bwd: bad shape");
@@ -952,14 +952,27 @@ extern "C" int htrvt_pool_tokens_bwd(const void* dtok, const void* x, const floa
   if (H == 2) {
     const long long threads = (long long)B * W * (D / ch);
     DISPATCH_T(dtype, hipLaunchKernelGGL(pool_tokens_bwd_h2_kernel<T>, dim3((unsigned)((threads + NT - 1) / NT)), dim3(NT), 0,
-                                         (hipStream_t)stream, (const T*)dtok, (const T*)x, keep, (T*)dx, B, W, D));
+                                         (hipStream_t)stream, (const T*)dtok, (const T*)x, keep, keep_ld, (T*)dx, B, W, D));
     return check_launch("pool_tokens_bwd");
   }
   const long long total = (long long)B * H * W * (D / ch);
   dim3 grid(grid_for(total));
   DISPATCH_T(dtype, hipLaunchKernelGGL(pool_tokens_bwd_kernel<T>, grid, dim3(NT), 0, (hipStream_t)stream, (const T*)dtok,
-                                       (const T*)x, keep, (T*)dx, B, H, W, D));
+                                       (const T*)x, keep, keep_ld, (T*)dx, B, H, W, D));
   return check_launch("pool_tokens_bwd");
+}
+
+extern "C" int htrvt_pool_tokens_bwd(const void* dtok, const void* x, const float* keep, void* dx, int B, int H, int N,
+                                     int D, int dtype, void* stream) {
+  return pool_tokens_bwd_launch(dtok, x, keep, 0, dx, B, H, N, D, dtype, stream);
+}
+
+extern "C" int htrvt_pool_tokens_bwd_ps(const void* dtok, const void* x, const float* keep, int keep_ld, void* dx, int B,
+                                        int H, int N, int D, int dtype, void* stream) {
+  HTRVT_REQUIRE(keep_ld == 0 || keep_ld == N, "htrvt_pool_tokens_bwd_ps: keep_ld=%d is neither 0 ([N] mask) nor N=%d ([B][N] mask)",
+                keep_ld, N);
+  HTRVT_REQUIRE(keep != nullptr || keep_ld == 0, "htrvt_pool_tokens_bwd_ps: a row stride without a mask");
+  return pool_tokens_bwd_launch(dtok, x, keep, keep_ld, dx, B, H, N, D, dtype, stream);
 }
 
 extern "C" int htrvt_conv1_wgrad_blocks(int B, int H) {

@@ -745,7 +745,7 @@ __global__ __launch_bounds__(NT) void bn_relu_maxpool_kernel(const T* __restrict
 // ------------------------------------------------------------------ final maxpool + span mask + pos-embed -> tokens
 template <typename T>
 __global__ __launch_bounds__(NT) void pool_tokens_kernel(const T* __restrict__ x, const float* __restrict__ keep,
-                                                         const float* __restrict__ mask_token,
+                                                         int keep_ld, const float* __restrict__ mask_token,
                                                          const float* __restrict__ pos, T* __restrict__ tok, int B, int H,
                                                          int W, int D) {
   constexpr int CH = Vec16<T>::N;
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(NT) void pool_tokens_kernel(const T* __restrict__ x
     const int n = (int)(t % N), b = (int)(t / N);
     const int ho = n / W, wo = n - ho * W;
     float m[CH];
-    const bool kept = keep == nullptr || keep[n] != 0.f;
+    const bool kept = keep == nullptr || keep[(long long)b * keep_ld + n] != 0.f;   // keep_ld 0: one [N] mask for the batch
     if (kept) {
 #pragma unroll
       for (int j = 0; j < CH; ++j) m[j] = -INFINITY;
@@ -966,8 +966,8 @@ extern "C" int htrvt_bn_relu_maxpool(const void* x, const float* scale, const fl
   return check_launch("bn_relu_maxpool");
 }
 
-extern "C" int htrvt_pool_tokens(const void* x, const float* keep, const float* mask_token, const float* pos, void* tok,
-                                 int B, int H, int N, int D, int dtype, void* stream) {
+static int pool_tokens_launch(const void* x, const float* keep, int keep_ld, const float* mask_token, const float* pos,
+                              void* tok, int B, int H, int N, int D, int dtype, void* stream) {
   const int ch = dtype == HTRVT_BF16 ? 8 : 4;
   const int Ho = (H - 1) / 2 + 1;
   HTRVT_REQUIRE(D % ch == 0 && N % Ho == 0, "htrvt_pool_tokens: bad shape D=%d N=%d H=%d", D, N, H);
@@ -975,10 +975,23 @@ extern "C" int htrvt_pool_tokens(const void* x, const float* keep, const float* 
   const long long total = (long long)B * N * (D / ch);
   dim3 grid(grid_for(total));
   if (dtype == HTRVT_BF16)
-    hipLaunchKernelGGL(pool_tokens_kernel<bf16_t>, grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, keep,
+    hipLaunchKernelGGL(pool_tokens_kernel<bf16_t>, grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, keep, keep_ld,
                        mask_token, pos, (bf16_t*)tok, B, H, W, D);
   else
-    hipLaunchKernelGGL(pool_tokens_kernel<float>, grid, dim3(NT), 0, (hipStream_t)stream, (const float*)x, keep, mask_token,
-                       pos, (float*)tok, B, H, W, D);
+    hipLaunchKernelGGL(pool_tokens_kernel<float>, grid, dim3(NT), 0, (hipStream_t)stream, (const float*)x, keep, keep_ld,
+                       mask_token, pos, (float*)tok, B, H, W, D);
   return check_launch("pool_tokens");
+}
+
+extern "C" int htrvt_pool_tokens(const void* x, const float* keep, const float* mask_token, const float* pos, void* tok,
+                                 int B, int H, int N, int D, int dtype, void* stream) {
+  return pool_tokens_launch(x, keep, 0, mask_token, pos, tok, B, H, N, D, dtype, stream);
+}
+
+extern "C" int htrvt_pool_tokens_ps(const void* x, const float* keep, int keep_ld, const float* mask_token,
+                                    const float* pos, void* tok, int B, int H, int N, int D, int dtype, void* stream) {
+  HTRVT_REQUIRE(keep_ld == 0 || keep_ld == N, "htrvt_pool_tokens_ps: keep_ld=%d is neither 0 ([N] mask) nor N=%d ([B][N] mask)",
+                keep_ld, N);
+  HTRVT_REQUIRE(keep != nullptr || keep_ld == 0, "htrvt_pool_tokens_ps: a row stride without a mask");
+  return pool_tokens_launch(x, keep, keep_ld, mask_token, pos, tok, B, H, N, D, dtype, stream);
 }

@@ -72,7 +72,7 @@ class ModelShape:
 
     def __init__(self, nb_cls, img_size, embed_dim, depth, num_heads, mlp_ratio=4.0, patch_size=(4, 64), ln_eps=LN_EPS,
                  pos_embed=True, whiten_logits=True, relpos=None, table_patches=None, dropout=False, lgp=None, pos_table=None,
-                 local=None):
+                 local=None, whiten_input=True):
         """The switches of the window-attention fork (model_window/model/HTR_VT.py), defaults = model_v1:
         pos_embed: tokens get the absolute position embedding; whiten_logits: the parameter-free LayerNorm over the logits;
         relpos: None, or per block (window, shift) -- attention with the block's relative-position table
@@ -87,8 +87,12 @@ class ModelShape:
         local: per block None (the v1 full-attention block) or (window, shift) -- a LocalBlock1D: the v1 block with its
         attention inside windows of `window` tokens rolled by `shift` (csrc/lgp.hip; padding slots = the qkv bias, no mask
         across the wrap).  v1 parameter names and the v1 position table `pos_embed`, whose num_patches rows must be the
-        tokens the stem leaves (any W that is a multiple of 8 for which the two agree)."""
+        tokens the stem leaves (any W that is a multiple of 8 for which the two agree).
+        whiten_input: the parameter-free LayerNorm over each input image in front of the stem (HTR_VT.py:224).  False for
+        the multi-mask forks model_sgm_mms_attach / _detach, whose forward_features hands the image to the ResNet as it is
+        (model_sgm_mms_attach/model/HTR_VT.py:364): the stem kernels then get the statistics (mean 0, rstd 1)."""
         self.nb_cls = int(nb_cls)
+        self.whiten_input = bool(whiten_input)
         self.pos_embed, self.whiten_logits, self.dropout = bool(pos_embed), bool(whiten_logits), bool(dropout)
         self.relpos = None if relpos is None else [None if g is None else (int(g[0]), int(g[1])) for g in relpos]
         self.ln_eps = float(ln_eps)
@@ -187,6 +191,7 @@ class Engine:
         self._saved_planes, self._saving = {}, False    # forward(save=True): id(activation) -> its hi / lo planes, for the weight gradients
         self._packs = {}      # name -> (version key, tensors)
         self.weights_epoch = 0   # bumped by whoever rewrites parameters through raw pointers (Trainer.optimizer_step)
+        self._unit_stats = None      # whiten_input=False: {mean 0, rstd 1} per image, made once per batch size
         self.fuse_conv1_backward = True   # conv1/bn1/maxpool backward as per-channel sums over the pooled gradient
         self.fuse_bn_backward = True   # bf16: ReLU mask + BN-backward sums in the dgrad epilogue (False: separate pass)
         self.overlap_wgrad = True      # weight-gradient GEMMs on a side stream
@@ -924,7 +929,8 @@ class Engine:
     # ------------------------------------------------------------------ forward
     def forward(self, P, img, keep_mask=None, train=False, save=False, want_features=False):
         """P: dict name -> float32 device tensor (parameters and BN buffers, reference state_dict names).
-        img: [B,1,H,W] float32.  keep_mask: None or float32 [N] (1 keep / 0 mask-token).
+        img: [B,1,H,W] float32.  keep_mask: None, [N] (1 keep / 0 mask-token, one mask for the batch) or [B,N] / [B,N,1]
+        (one mask per image, the multi-mask forks); any other shape is a ValueError.
         Returns float32 logits [B,N,nb_cls] (after the final param-free LayerNorm); want_features: (logits, feats) with
         feats the final norm's output as a fresh float32 [B,N,D] tensor (the SGM forks' feature tap)."""
         B, u8, keep = self._begin_forward(img, keep_mask, train, want_features)
@@ -973,7 +979,14 @@ class Engine:
             self._call_started.record()
         keep = None
         if keep_mask is not None:   # uploaded before anything is enqueued: a pageable host->device copy waits for the stream
+            N = s.num_patches
+            shape = tuple(keep_mask.shape)
+            if shape not in ((N,), (B, N), (B, N, 1)):
+                raise ValueError(f"keep_mask of shape {shape}: expected [{N}] (one mask for the batch), or [{B}, {N}] / "
+                                 f"[{B}, {N}, 1] (one mask per image of this batch of {B})")
             keep = keep_mask.to(dtype=torch.float32).contiguous()
+            if len(shape) > 1:      # per-sample rows (the multi-mask forks): _tokens_fwd / _tokens_bwd see keep.dim() == 2
+                keep = keep.view(B, N)
             if not keep.is_cuda:    # through pinned memory: a pageable copy would make the host wait for the previous step
                 keep = keep.pin_memory().to(self.dev, non_blocking=True)
         return B, u8, keep
@@ -1024,8 +1037,13 @@ class Engine:
         """whitening statistics + conv1 + BN + ReLU + maxpool (resnet18.py:74-77): the pooled activations [B,Hp,W,D/4]"""
         st, C1 = stream(), self.s.D // 4
         B, _, H, W = img.shape
-        stats = self._empty(B, 2, dtype=torch.float32)
-        check(lib.htrvt_img_stats(ptr(img), ptr(stats), B, H * W, WHITEN_EPS, u8, st), "img_stats")
+        if self.s.whiten_input:
+            stats = self._empty(B, 2, dtype=torch.float32)
+            check(lib.htrvt_img_stats(ptr(img), ptr(stats), B, H * W, WHITEN_EPS, u8, st), "img_stats")
+        else:       # the kernels whiten with (pixel - mean) * rstd: {0, 1} per image leaves the pixels as they are
+            if self._unit_stats is None or self._unit_stats.shape[0] != B:
+                self._unit_stats = torch.tensor([0.0, 1.0], device=self.dev).repeat(B, 1)
+            stats = self._unit_stats
         w1 = P["patch_embed.conv1.weight"]
         Hp = (H // 2 - 1) // 2 + 1
         a = self._empty(B, Hp, W, C1)
@@ -1123,8 +1141,12 @@ class Engine:
             if self._zero_pos is None or self._zero_pos.shape != (N, D):
                 self._zero_pos = torch.zeros(N, D, dtype=torch.float32, device=self.dev)
             pos = self._zero_pos
-        check(lib.htrvt_pool_tokens(ptr(x), ptr(keep), ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D, self.dti, st),
-              "pool_tokens")
+        if keep is not None and keep.dim() == 2:    # [B, N]: one mask row per sample
+            check(lib.htrvt_pool_tokens_ps(ptr(x), ptr(keep), N, ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D,
+                                           self.dti, st), "pool_tokens_ps")
+        else:
+            check(lib.htrvt_pool_tokens(ptr(x), ptr(keep), ptr(P["mask_token"]), ptr(pos), ptr(tok), B, Hc, N, D, self.dti, st),
+                  "pool_tokens")
         if sv is not None:
             sv["l3"], sv["keep"], sv["l3_shape"] = x, keep, (B, Hc, Wc)
         return tok, N
@@ -1387,12 +1409,17 @@ class Engine:
         """token assembly: the mask token's gradient and the gradient of the layer-3 output"""
         st, M, D = stream(), B * N, self.s.D
         keep = sv["keep"]
-        if keep is not None:
-            ops.colsum(dx, M, D, D, G["mask_token"], dti=self.dti, keep=keep, keep_mod=N)
+        per_sample = keep is not None and keep.dim() == 2
+        if keep is not None:        # a [B, N] mask is one flag per token row: keep_mod = B N
+            ops.colsum(dx, M, D, D, G["mask_token"], dti=self.dti, keep=keep, keep_mod=M if per_sample else N)
         Bq, Hc, Wc = sv["l3_shape"]
         dfeat = self._empty(Bq, Hc, Wc, D)
-        check(lib.htrvt_pool_tokens_bwd(ptr(dx), ptr(sv["l3"]), ptr(keep), ptr(dfeat), B, Hc, N, D, self.dti, st),
-              "pool_tokens_bwd")
+        if per_sample:
+            check(lib.htrvt_pool_tokens_bwd_ps(ptr(dx), ptr(sv["l3"]), ptr(keep), N, ptr(dfeat), B, Hc, N, D, self.dti, st),
+                  "pool_tokens_bwd_ps")
+        else:
+            check(lib.htrvt_pool_tokens_bwd(ptr(dx), ptr(sv["l3"]), ptr(keep), ptr(dfeat), B, Hc, N, D, self.dti, st),
+                  "pool_tokens_bwd")
         return dfeat
 
     def _stem_bwd(self, P, G, sv, dfeat, B, after_layer3):

@@ -68,6 +68,29 @@ def residual_dropout(x, res, rows_per_sample, seeds, p, p_path):
     return y
 
 
+def mask_tokens_fwd(x, keep, mask_token):
+    """y[r] = x[r] where keep[r % keep.numel()] != 0, else mask_token: x [rows, D] float32 / bfloat16, keep float32 with N
+    (one mask for the batch) or rows (one flag per row: a [B, N] mask) elements, mask_token float32 [D]"""
+    y = torch.empty_like(x)
+    check(lib.htrvt_mask_tokens_fwd(ptr(x), ptr(keep), keep.numel(), ptr(mask_token), ptr(y), x.shape[0], x.shape[1],
+                                    dt(x.dtype), stream()), "mask_tokens_fwd")
+    return y
+
+
+def mask_tokens_bwd(dy, keep, want_token_grad=True):
+    """(dx, d mask_token) of mask_tokens_fwd: dx = dy where kept and 0 where masked; d mask_token [D] float32 = the sum of
+    dy over the masked rows through htrvt_colsum's row filter (fixed order, no float atomics), None when not wanted"""
+    rows, D = dy.shape
+    dx = torch.empty_like(dy)
+    check(lib.htrvt_mask_tokens_bwd(ptr(dy), ptr(keep), keep.numel(), ptr(dx), rows, D, dt(dy.dtype), stream()),
+          "mask_tokens_bwd")
+    dtoken = None
+    if want_token_grad:
+        dtoken = torch.zeros(D, dtype=torch.float32, device=dy.device)
+        colsum(dy, rows, D, D, dtoken, dti=dt(dy.dtype), keep=keep, keep_mod=keep.numel())
+    return dx, dtoken
+
+
 def _heads(qkv, h):
     """(D, hd) of qkv [B*N, 3*D], D = h * hd"""
     D = qkv.shape[1] // 3

@@ -137,7 +137,8 @@ class Trainer:
 
     def _forward_backward_staged(self, img, staged, keep_mask):
         """the device work of forward_backward: label arrays already on the device (`staged`), keep_mask None or a host /
-        device [N] tensor.  This is the body a captured step records (GraphedStep)."""
+        device [N] tensor, or [B, N] / [B, N, 1] with one mask per image (Engine.forward).  This is the body a captured
+        step records (GraphedStep, with an [N] mask only)."""
         from .ctc import ctc_forward_backward
         eng, fl = self.engine, self.flat
         fl.flat_g.zero_()
@@ -287,6 +288,9 @@ class GraphedStep:
         if self._engine_plan(tr.engine) != self._plan:
             raise RuntimeError("GraphedStep: the engine's switches changed since the capture (the graph holds the launches of the "
                                "plan it was recorded with): capture the step again")
+        if keep_mask is not None and tuple(keep_mask.shape) != (self.N,):
+            raise ValueError(f"GraphedStep was captured with one [{self.N}] mask buffer for the batch, got a keep_mask of shape "
+                             f"{tuple(keep_mask.shape)}: per-sample masks run through Trainer.step")
         if self._staged is not None:
             self._staged.synchronize()      # previous step's host->device copies have run: the pinned buffers are free
         tl = np.asarray(lengths, dtype=np.int32).reshape(-1)

@@ -8,7 +8,9 @@ batched-GEMM route), the SGM head's single-head cross-attention, the LGP block's
 and scaled up-sampling, the macaron forks' GLU + depthwise token convolution + BatchNorm + SiLU, the VAN forks' depthwise
 Conv2d (depthwise_conv2d), the Swin fork's 2-D shifted-window attention (window_attention_2d), and the forks' regularisers
 as operators: dropout on the attention probabilities (self_attention, relpos_self_attention(dropout_p=...)) and
-residual + drop_path(dropout(x)) (residual_dropout); wiring those into the models is not done here.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
+residual + drop_path(dropout(x)) (residual_dropout); wiring those into the models is not done here.  mask_tokens is the
+multi-mask forks' per-sample token masking x * keep + (1 - keep) * mask_token as an operator (csrc/masking.hip), for stems
+that do not end in the ResNet's token assembly.  What stays here is wrapper logic: dtype checks, padding a sequence to the length the kernels
 run at, and the index bookkeeping (which table entry each (query, key) pair uses), host glue for the CPU tests."""
 import torch
 
@@ -266,6 +268,42 @@ def residual_dropout(x, res, B, p, p_path, seeds=None):
     if seeds is not None and (seeds.dtype != torch.int64 or seeds.numel() != 2 or not seeds.is_cuda):
         raise TypeError("seeds: an int64 device tensor of two elements expected")
     return _ResidualDropout.apply(x, res, x.shape[0] // B, seeds, float(p), float(p_path))
+
+
+class _MaskTokens(torch.autograd.Function):
+    """x [rows, D], keep float32 [N] or [rows], mask_token float32 [D] -> y (seq_ops.mask_tokens_fwd / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, x, keep, mask_token):
+        ctx.save_for_backward(keep)
+        return seq_ops.mask_tokens_fwd(x, keep, mask_token)
+
+    @staticmethod
+    def backward(ctx, dy):
+        keep, = ctx.saved_tensors
+        dx, dtoken = seq_ops.mask_tokens_bwd(dy.contiguous(), keep, ctx.needs_input_grad[2])
+        return dx, None, dtoken
+
+
+def mask_tokens(x, keep, mask_token):
+    """The multi-mask forks' x * keep + (1 - keep) * mask_token (model_sgm_mms_attach/model/HTR_VT.py:377) for a keep
+    mask of zeros and ones: x [B, N, D] float32 or bfloat16 (D a multiple of 4 / 8); keep [B, N] or [B, N, 1] (one mask
+    per sample) or [N] (one for the batch), any dtype, non-zero = keep; mask_token a float32 parameter of D elements
+    ([D] or the forks' [1, 1, D]).  Returns y like x.  Differentiable in x (dy where kept, 0 where masked) and in
+    mask_token (the sum of dy over the masked tokens, in float32 and a fixed order: two runs agree bitwise)."""
+    _need_device(x, keep, mask_token)
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("mask_tokens: x [B, N, D] float32 or bfloat16 expected")
+    B, N, D = x.shape
+    if tuple(keep.shape) not in ((N,), (B, N), (B, N, 1)):
+        raise ValueError(f"mask_tokens: keep of shape {tuple(keep.shape)}: [{N}], [{B}, {N}] or [{B}, {N}, 1] expected")
+    if mask_token.dtype != torch.float32 or mask_token.numel() != D:
+        raise ValueError(f"mask_tokens: mask_token: float32 with {D} elements expected")
+    if D % (4 if x.dtype == torch.float32 else 8):
+        raise ValueError(f"mask_tokens: D = {D} is no multiple of {4 if x.dtype == torch.float32 else 8}")
+    k = keep.to(torch.float32).contiguous().view(-1)
+    token = mask_token.contiguous().view(D)
+    return _MaskTokens.apply(x.contiguous().view(B * N, D), k, token).view(B, N, D)
 
 
 class _CrossAttention(torch.autograd.Function):

@@ -182,6 +182,22 @@ int htrvt_bn_relu_maxpool(const void* x, const float* scale, const float* shift,
 /* tokens[b][n][:] = (keep[n] ? maxpool(x)[b,0,n,:] : mask_token) + pos[n][:];  x NHWC [B,H(<=3),N,D] */
 int htrvt_pool_tokens(const void* x, const float* keep, const float* mask_token, const float* pos, void* tok,
                       int B, int H, int N, int D, int dtype, void* stream);
+/* the same with one mask row per sample (the multi-mask forks' x * keep + (1 - keep) * mask_token with keep [B, L, 1],
+ * model_sgm_mms_attach/model/HTR_VT.py:368-377): sample b, token n reads keep[b * keep_ld + n].  keep_ld = N: keep is
+ * float32 [B][N]; keep_ld = 0: the shared [N] mask, bitwise htrvt_pool_tokens (same kernel).  Other strides are refused. */
+int htrvt_pool_tokens_ps(const void* x, const float* keep, int keep_ld, const float* mask_token, const float* pos,
+                         void* tok, int B, int H, int N, int D, int dtype, void* stream);
+
+/* ---- stand-alone token masking (csrc/masking.hip), for stems that do not end in htrvt_pool_tokens ---------------
+ * ATen: y = x * keep + (1 - keep) * mask_token, keep in {0, 1} (HTR_VT.py:377 of the mms forks; svtr.py masks at D = 64).
+ * x, y [rows][D] float32 / bfloat16 (D a multiple of 4 / 8), mask_token float32 [D], keep float32 [keep_mod]: row r is
+ * kept where keep[r % keep_mod] != 0 (keep_mod = N: one [N] mask for the batch; keep_mod = rows = B N: a [B][N] mask).
+ * Backward: dx = dy where kept, 0 where masked; d mask_token[D] += sum of dy over the masked rows is
+ * htrvt_colsum(dy, rows, D, D, out, keep, keep_mod, ...) -- the same row rule, a fixed summation order, no float atomics. */
+int htrvt_mask_tokens_fwd(const void* x, const float* keep, int64_t keep_mod, const float* mask_token, void* y,
+                          int64_t rows, int D, int dtype, void* stream);
+int htrvt_mask_tokens_bwd(const void* dy, const float* keep, int64_t keep_mod, void* dx, int64_t rows, int D, int dtype,
+                          void* stream);
 
 /* ---- encoder helpers (HTR_VT.py:27-39,68-83,169-170,236-239) ------------------ */
 int htrvt_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
@@ -263,6 +279,10 @@ int htrvt_maxpool_bwd(const void* dpool, const uint8_t* idx, const void* x, cons
 /* backward of htrvt_pool_tokens w.r.t. x (masked tokens pass no gradient) */
 int htrvt_pool_tokens_bwd(const void* dtok, const void* x, const float* keep, void* dx, int B, int H, int N, int D,
                           int dtype, void* stream);
+/* backward of htrvt_pool_tokens_ps: keep[b * keep_ld + n], keep_ld = N or 0 (0: bitwise htrvt_pool_tokens_bwd); both the
+ * general kernel and the H == 2 kernel take the stride */
+int htrvt_pool_tokens_bwd_ps(const void* dtok, const void* x, const float* keep, int keep_ld, void* dx, int B, int H,
+                             int N, int D, int dtype, void* stream);
 /* dW[C][9] += sum_pix dY * whitened-input tap (autograd of htrvt_conv1_fwd); partial: [blocks][C*9] float32 scratch */
 int htrvt_conv1_wgrad_blocks(int B, int H);
 int htrvt_conv1_wgrad(const void* img, const float* stats, const void* dy, float* dw, float* partial,
