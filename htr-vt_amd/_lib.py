@@ -148,6 +148,8 @@ PROTOTYPES = {
     "htrvt_attn_relpos_dropout_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32, vp, f32,
                                             i32, vp]),
     "htrvt_residual_dropout": (i32, [vp, vp, vp, i32, i64, i32, vp, f32, f32, i32, vp]),
+    "htrvt_drop_add_ln_fwd": (i32, [vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]),
+    "htrvt_layernorm_bwd_drop": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, i64, i32, i32, vp]),
     "htrvt_sgm_xent_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "htrvt_sgm_xent_bwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "htrvt_sgm_convert": (i32, [vp, i32, vp, i32, i64, i32, vp]),

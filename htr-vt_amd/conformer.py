@@ -21,12 +21,27 @@ parity route), and csrc/gnmixer.hip for GLU + depthwise convolution + GroupNorm(
 and FeedForward's SiLU.  GroupNorm takes the statistics of each image in train and eval mode alike.  Tokens stay [B*N, D]
 rows throughout.  Every parameter gradient is float32 and bitwise reproducible.
 compute_dtype: torch.float32 (parity) or torch.bfloat16; inputs and outputs are float32.
-ConvModule's dropout is active in train mode: its mask comes from a counter-based generator seeded by int64s drawn on the
-device from the CUDA default generator, and is regenerated in the backward.  Not served, refused with an error: in train mode a
-non-zero ff_dropout (FeedForward's dropout, the attention's proj_drop), attn_dropout or drop_path; ConvModule's drop_path > 0
-in train mode; hidden widths whose GLU output is not a multiple of 8; an odd hidden width (the fork's no-GLU path);
-kernel sizes other than odd 1 ... 15; head widths other than 32 / 64 / 128.  The fork's x + drop_path(conv_out - x) is
-computed as x + branch.
+
+Train mode runs every regulariser the constructors take, with the forks' semantics: dropout behind the feed-forwards and the
+attention's projection (ff_dropout), on the attention probabilities (attn_dropout) and behind the conv branch
+(conv_dropout / ConvModule's dropout); four independent DropPath draws per block, one per residual site, by timm's rule
+(one Bernoulli(1 - p) per sample, kept samples scaled by 1 / (1 - p)); SqueezeFormerEncoder ramps the blocks' rate up to
+drop_path_total.  x + 1/2 drop_path(dropout(lin2(...))) is computed as x + drop_path(dropout(1/2 lin2(...))), and the fork's
+x + drop_path(conv_out - x) as x + drop_path(dropout(branch)).  With a regulariser active the GEMM that ends a branch writes
+the branch alone and ONE launch of csrc/dropnorm.hip forms the new residual stream and the LayerNorm behind it (backward:
+that norm's backward and the branch's masked gradient); behind the SE gate of SqueezeConformerBlock the conv site is
+seq_ops.residual_dropout and the plain norm.  With every rate zero, and in eval mode, the launches are those without
+regularisers, the adds in the GEMM epilogues.
+Masks come from a counter-based generator (csrc/dropout_common.h) keyed by int64 seeds and the element's / sample's index:
+nothing is stored, the backward regenerates them.  The seeds are drawn on the device from the CUDA default generator, one
+draw per forward of a node and no host sync, distinct per site and per block; `torch.cuda.manual_seed(s)` before two
+identical steps gives identical bits.  A module keeps the seeds of its last train-mode forward as `last_drop_seeds` (layout
+in the class docstrings), so the masks can be rebuilt outside.
+Not served, refused with an error: train mode with a non-zero rate on a tensor that is not on the device (the seeds are drawn
+there; the error names the rates); attn_dropout > 0 in train mode where the attention takes the unfused route with a padded
+token count (float32 with N off a multiple of 4; bfloat16 with N < 32 off a multiple of 8); hidden widths whose GLU output is
+not a multiple of 8; an odd hidden width (the fork's no-GLU path); kernel sizes other than odd 1 ... 15; head widths other
+than 32 / 64 / 128.
 """
 import torch
 import torch.nn as nn
@@ -54,9 +69,30 @@ def _params(names, params, cdt):
     return P
 
 
-def _seeds(p, dev):
-    """(seeds, p) of a dropout with rate p, seeds drawn on the device (CUDA default generator, no sync); None for p = 0"""
-    return (torch.randint(0, 2 ** 62, (2,), dtype=torch.int64, device=dev), float(p)) if p > 0 else None
+SITES = ("ffn1", "attn", "conv", "ffn2")          # the residual sites of a block, in the order of its forward
+BLOCK_SEEDS = 2 * len(SITES) + 1                  # (element, sample) per site, then the attention probabilities'
+
+
+def _draw(n, dev):
+    """n int64 seeds on the device: one draw from the CUDA default generator, no host sync"""
+    return torch.randint(0, 2 ** 62, (n,), dtype=torch.int64, device=dev)
+
+
+def _rates_need_device(mod, x, **rates):
+    """Train mode with a non-zero rate draws the masks' seeds from the CUDA generator of x's device, so a tensor that is not
+    on one is refused here, before anything is drawn, and the refusal names the rates that ask for it.  (Eval mode, and train
+    mode with every rate zero, draw nothing and reach the generic device check of _apply.)"""
+    on = {n: p for n, p in rates.items() if p > 0}
+    if mod.training and on and not x.is_cuda:
+        raise NotImplementedError(
+            f"{type(mod).__name__}: " + ", ".join(f"{n} = {p}" for n, p in on.items()) + " in train mode is served on an MI355X "
+            f"only: the masks' seeds are drawn on the device and x is on {x.device} (move the module and its input to cuda, or "
+            "call .eval())")
+
+
+def _site(p, p_path, seeds):
+    """a residual site's (p, p_path, seeds) for seq_ops, None when both rates are 0"""
+    return (float(p), float(p_path), seeds) if p > 0 or p_path > 0 else None
 
 
 class _Function(torch.autograd.Function):
@@ -103,17 +139,10 @@ def _names(mod):
     return tuple(n for n, _ in mod.named_parameters())
 
 
-def _refuse(mod, **rates):
-    """train mode with a regulariser this implementation does not draw"""
-    if mod.training:
-        for n, p in rates.items():
-            if p > 0:
-                raise NotImplementedError(f"{type(mod).__name__}: {n} = {p} in train mode is not served (set it to 0, or "
-                                          f"call .eval()); ConvModule's own dropout is")
-
-
 class FeedForward(nn.Module):
-    """Position-wise feed forward: lin2(silu(lin1(x))), dropout behind it (train mode: rate 0 only)"""
+    """Position-wise feed forward: dropout(lin2(silu(lin1(x)))).  After a train-mode forward with dropout > 0,
+    last_drop_seeds is the int64 device tensor [2] it drew: [0] keys the element mask (seq_ops.residual_dropout's element
+    key over the rows [B*N, dim]), [1] is not used."""
 
     def __init__(self, dim, hidden_dim, dropout=0.1, activation=nn.SiLU, compute_dtype=torch.float32):
         super().__init__()
@@ -127,23 +156,33 @@ class FeedForward(nn.Module):
         self.lin2 = nn.Linear(hidden_dim, dim)
         self.dropout = nn.Dropout(dropout)
         self.compute_dtype = compute_dtype
+        self.last_drop_seeds = None
         self.PARAMS = _names(self)
 
     def _fwd(self, xr, P, xshape):
         y, saved = seq_ops.silu_ffn_fwd(xr, *[P[n] for n in seq_ops.FFN_NAMES])
-        return y, saved, None, xshape
+        drop = None
+        if self.training and self.dropout.p > 0:
+            self.last_drop_seeds = _draw(2, xr.device)
+            drop = (xshape[1], self.last_drop_seeds, float(self.dropout.p), 0.0)
+            y = seq_ops.residual_dropout(y, None, *drop)
+        return y, saved, drop, xshape
 
-    def _bwd(self, dy, xr, P, saved, geo):
+    def _bwd(self, dy, xr, P, saved, drop):
+        if drop is not None:
+            dy = seq_ops.residual_dropout(dy, None, *drop)
         dx, g = seq_ops.silu_ffn_bwd(dy, xr, P["lin1.weight"], P["lin2.weight"], saved)
         return dx, dict(zip(seq_ops.FFN_NAMES, g))
 
     def forward(self, x):
-        _refuse(self, dropout=self.dropout.p)
+        _rates_need_device(self, x, dropout=self.dropout.p)
         return _apply(self, x, self.lin1.in_features)
 
 
 class ConvModule(nn.Module):
-    """LN -> 1x1 conv -> GLU -> depthwise conv -> GroupNorm(1, C) -> SiLU -> 1x1 conv -> dropout -> + x, on x [B, N, dim]"""
+    """LN -> 1x1 conv -> GLU -> depthwise conv -> GroupNorm(1, C) -> SiLU -> 1x1 conv -> dropout -> drop_path -> + x, on
+    x [B, N, dim].  After a train-mode forward with a non-zero rate, last_drop_seeds is the int64 device tensor [2] it drew:
+    [0] keys the element mask, [1] the drop-path's sample mask (seq_ops.residual_dropout's keys)."""
 
     def __init__(self, dim, kernel_size=3, dropout=0.1, drop_path=0.0, expansion=1.0, compute_dtype=torch.float32):
         super().__init__()
@@ -169,10 +208,14 @@ class ConvModule(nn.Module):
         self.drop_path = nn.Identity()
         self.drop_path_rate = float(drop_path)
         self.compute_dtype = compute_dtype
+        self.last_drop_seeds = None
         self.PARAMS = _names(self)
 
     def _drop(self, dev):
-        return _seeds(self.dropout.p if self.training else 0.0, dev)
+        if not self.training or not (self.dropout.p > 0 or self.drop_path_rate > 0):
+            return None
+        self.last_drop_seeds = _draw(2, dev)
+        return _site(self.dropout.p, self.drop_path_rate, self.last_drop_seeds)
 
     def _fwd(self, xr, P, xshape):
         geo = (xshape[0], xshape[1], self._drop(xr.device))
@@ -183,7 +226,7 @@ class ConvModule(nn.Module):
         return seq_ops.conv_module_bwd(dy, xr, P, saved, *geo)
 
     def forward(self, x):
-        _refuse(self, drop_path=self.drop_path_rate)
+        _rates_need_device(self, x, dropout=self.dropout.p, drop_path=self.drop_path_rate)
         return _apply(self, x, self.layer_norm.normalized_shape[0])
 
 
@@ -209,7 +252,16 @@ class Attention(nn.Module):
 
 
 class ConformerBlock(nn.Module):
-    """x + 1/2 FFN -> x + MHSA -> x + ConvModule's branch -> x + 1/2 FFN -> LayerNorm"""
+    """x + 1/2 drop_path(FFN) -> x + drop_path(MHSA) -> x + drop_path(ConvModule's branch) -> x + 1/2 drop_path(FFN) ->
+    LayerNorm, with dropout ff_dropout behind both feed-forwards and the attention's projection, attn_dropout on the attention
+    probabilities and conv_dropout behind the conv branch.
+
+    After a train-mode forward with a non-zero rate, last_drop_seeds is the int64 device tensor [BLOCK_SEEDS = 9] it drew
+    (one draw per forward; the backward re-uses it):
+        [2 i], [2 i + 1]   site i of SITES = (ffn1, attn, conv, ffn2): the element mask's and the drop-path sample mask's seed,
+                           seq_ops.residual_dropout's keys over the rows [B*N, dim]
+        [8]                the attention probabilities' mask, the key of seq_ops' `drop=` over [B, heads, N, N]
+    A block whose only rate is conv_dropout draws these nine too (before the other rates were served it drew two)."""
     SQUEEZE = False
 
     def __init__(self, dim, num_heads, num_patches, mlp_ratio=4.0, ff_dropout=0.1, attn_dropout=0.0, conv_dropout=0.0,
@@ -232,31 +284,63 @@ class ConformerBlock(nn.Module):
         self.ffn2_norm = norm_layer(dim, elementwise_affine=True)
         self.ffn2 = FeedForward(dim, ff_hidden, dropout=ff_dropout, compute_dtype=compute_dtype)
         self.final_norm = norm_layer(dim, elementwise_affine=True)
-        for n in ("ffn1", "attn", "conv", "ffn2"):
+        for n in SITES:
             setattr(self, "drop_path_" + n, nn.Identity())
         self.drop_path_rate = float(drop_path)
         self.ff_dropout, self.attn_dropout = float(ff_dropout), float(attn_dropout)
         self.compute_dtype = compute_dtype
+        self.last_drop_seeds = None
         self.PARAMS = _names(self)
 
     def _eps(self):
         return dict(eps=self.ffn1_norm.eps, conv_eps=self.conv_module.layer_norm.eps, gn_eps=self.conv_module.norm.eps)
 
-    def _check_train(self):
-        _refuse(self, ff_dropout=self.ff_dropout, attn_dropout=self.attn_dropout, drop_path=self.drop_path_rate)
+    def _rates(self):
+        """the element-wise rate of each site, in the order of SITES"""
+        return (self.ffn1.dropout.p, self.attn.proj_drop.p, self.conv_module.dropout.p, self.ffn2.dropout.p)
+
+    def _regularised(self):
+        return self.training and (self.drop_path_rate > 0 or self.attn.attn_drop.p > 0 or any(p > 0 for p in self._rates()))
+
+    def _check_train(self, N):
+        """the one combination not served: dropout on the probabilities where the attention pads its token count"""
+        p = self.attn.attn_drop.p
+        if self.training and p > 0 and seq_ops.plain_attention_pads(self.compute_dtype, N):
+            raise NotImplementedError(
+                f"{type(self).__name__}: attn_dropout = {p} in train mode at N = {N} tokens is not served: in "
+                f"{str(self.compute_dtype).replace('torch.', '')} this N takes the attention route that pads the token count (N off "
+                "the 16-byte row), which draws no mask (set attn_dropout to 0, call .eval(), or use a multiple of "
+                f"{8 if self.compute_dtype == torch.bfloat16 else 4} tokens)")
+
+    def _check_device_for_rates(self, x):
+        ff, _, conv, _ = self._rates()
+        _rates_need_device(self, x, ff_dropout=ff, attn_dropout=self.attn.attn_drop.p, conv_dropout=conv,
+                           drop_path=self.drop_path_rate)
+
+    def _drops(self, seeds):
+        """the BlockDrop of seq_ops over this block's BLOCK_SEEDS seeds; None in eval mode and with every rate zero"""
+        if not self._regularised():
+            return None
+        self.last_drop_seeds = seeds
+        sites = [_site(p, self.drop_path_rate, seeds[2 * i:2 * i + 2]) for i, p in enumerate(self._rates())]
+        pa = self.attn.attn_drop.p
+        return seq_ops.BlockDrop(*sites, probs=(seeds[2 * len(SITES):], float(pa)) if pa > 0 else None)
 
     def _fwd(self, xr, P, xshape):
-        geo = (xshape[0], xshape[1], self.conv_module._drop(xr.device) if self.training else None)
+        drops = self._drops(_draw(BLOCK_SEEDS, xr.device)) if self._regularised() else None
+        geo = (xshape[0], xshape[1], drops)
         y, saved = seq_ops.conformer_block_fwd(xr, P, geo[0], geo[1], self.attn.num_heads, squeeze=self.SQUEEZE,
-                                               conv_drop=geo[2], **self._eps())
+                                               drops=drops, **self._eps())
         return y, saved, geo, xshape
 
     def _bwd(self, dy, xr, P, saved, geo):
         return seq_ops.conformer_block_bwd(dy, xr, P, saved, geo[0], geo[1], self.attn.num_heads, squeeze=self.SQUEEZE,
-                                           conv_drop=geo[2])
+                                           drops=geo[2])
 
     def forward(self, x):
-        self._check_train()
+        if x.dim() == 3:
+            self._check_train(x.shape[1])
+        self._check_device_for_rates(x)
         return _apply(self, x, self.ffn1_norm.normalized_shape[0])
 
 
@@ -344,7 +428,10 @@ class SqueezeConformerBlock(ConformerBlock):
 
 
 class SqueezeFormerEncoder(nn.Module):
-    """Two-stage SqueezeFormer encoder with one down-sampling and one up-sampling; input and output lengths are equal"""
+    """Two-stage SqueezeFormer encoder with one down-sampling and one up-sampling; input and output lengths are equal.
+    Block i (stage1, then stage2) takes the drop-path rate linspace(0, drop_path_total, depth)[i], as the fork does.
+    After a train-mode forward with a non-zero rate, last_drop_seeds is the int64 device tensor [blocks, BLOCK_SEEDS] of
+    one draw: row i is block i's last_drop_seeds (ConformerBlock names the columns)."""
 
     def __init__(self, dim, num_heads, num_patches, depth, mlp_ratio=4.0, ff_dropout=0.1, attn_dropout=0.0, conv_dropout=0.1,
                  conv_kernel_size=3, se_ratio=0.25, norm_layer=nn.LayerNorm, drop_path_total=0.1, compute_dtype=torch.float32):
@@ -368,6 +455,7 @@ class SqueezeFormerEncoder(nn.Module):
         self.fuse = nn.Identity()
         self.out_norm = norm_layer(dim, elementwise_affine=True)
         self.compute_dtype = compute_dtype
+        self.last_drop_seeds = None
         self.PARAMS = _names(self)
 
     def _blocks(self):
@@ -375,15 +463,25 @@ class SqueezeFormerEncoder(nn.Module):
 
     def _fwd(self, xr, P, xshape):
         blocks = self._blocks()
-        drops = [b.conv_module._drop(xr.device) if self.training else None for b in blocks]
+        drops = None
+        if any(b._regularised() for b in blocks):
+            seeds = _draw(len(blocks) * BLOCK_SEEDS, xr.device).view(len(blocks), BLOCK_SEEDS)
+            drops = [b._drops(seeds[i]) for i, b in enumerate(blocks)]
+            self.last_drop_seeds = seeds
         geo = (xshape[0], xshape[1], blocks[0].attn.num_heads, len(self.stage1), len(self.stage2), drops)
-        y, saved = seq_ops.squeezeformer_fwd(xr, P, *geo[:5], conv_drops=drops, **blocks[0]._eps())
+        y, saved = seq_ops.squeezeformer_fwd(xr, P, *geo[:5], drops=drops, **blocks[0]._eps())
         return y, saved, geo, xshape
 
     def _bwd(self, dy, xr, P, saved, geo):
-        return seq_ops.squeezeformer_bwd(dy, P, saved, *geo[:5], conv_drops=geo[5])
+        return seq_ops.squeezeformer_bwd(dy, P, saved, *geo[:5], drops=geo[5])
 
     def forward(self, x):
+        if x.dim() == 3:
+            N0 = x.shape[1]
+            for b in self.stage1:
+                b._check_train(N0)
+            for b in self.stage2:
+                b._check_train(N0 // 2 if N0 > 1 else N0)
         for b in self._blocks():
-            b._check_train()
+            b._check_device_for_rates(x)
         return _apply(self, x, self.out_norm.normalized_shape[0])

@@ -14,6 +14,8 @@ Dropout on the attention probabilities is the keyword `drop=(seed, p)` of the se
 device tensor of one element, p in (0, 1).  The mask is keep_elem(seed, ((b h + head) N + q) N + k) (csrc/dropout_common.h)
 on every route -- regenerated inside the fused kernels, drawn by htrvt_sgm_dropout on P and dP in the unfused one -- and a
 backward takes the forward's `drop`.  drop=None is the call without dropout, untouched."""
+import collections
+
 import torch
 
 from ._lib import check, lib
@@ -68,6 +70,18 @@ def residual_dropout(x, res, rows_per_sample, seeds, p, p_path):
     return y
 
 
+def drop_add_ln_fwd(x, res, rows_per_sample, seeds, p, p_path, gamma, beta, eps, save=True):
+    """residual_dropout and the LayerNorm behind it in one launch (csrc/dropnorm.hip) -> (s, y, mean, rstd):
+    s = res + drop_path(dropout(x)) with residual_dropout's masks and keys, y = LayerNorm(s) * gamma + beta with the
+    statistics (only under `save`) of s as it is stored, so (s, mean, rstd) is what layernorm_bwd / layernorm_bwd_drop take"""
+    rows, D = x.shape
+    s, y = torch.empty_like(x), torch.empty_like(x)
+    mean, rstd = (_f32(x, rows), _f32(x, rows)) if save else (None, None)
+    check(lib.htrvt_drop_add_ln_fwd(ptr(x), ptr(res), ptr(seeds), p, p_path, rows_per_sample, ptr(gamma), ptr(beta), ptr(s), ptr(y),
+                                    ptr(mean), ptr(rstd), rows, D, eps, dt(x.dtype), stream()), "drop_add_ln_fwd")
+    return s, y, mean, rstd
+
+
 def mask_tokens_fwd(x, keep, mask_token):
     """y[r] = x[r] where keep[r % keep.numel()] != 0, else mask_token: x [rows, D] float32 / bfloat16, keep float32 with N
     (one mask for the batch) or rows (one flag per row: a [B, N] mask) elements, mask_token float32 [D]"""
@@ -117,12 +131,30 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, dres=None):
     dx = torch.empty_like(x)
     check(lib.htrvt_layernorm_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(dx), ptr(partial),
                                   rows, D, dt(x.dtype), stream()), "layernorm_bwd")
+    _ln_param_grads(partial, nblk, D, dgamma, dbeta)
+    return dx
+
+
+def _ln_param_grads(partial, nblk, D, dgamma, dbeta):
     if dbeta.data_ptr() == dgamma.data_ptr() + 4 * D:   # weight and bias adjacent in one float32 buffer: one launch
         colsum(partial, nblk, 2 * D, 2 * D, dgamma, dti=0)
     else:
         colsum(partial, nblk, D, 2 * D, dgamma, dti=0)
         colsum(partial.data_ptr() + 4 * D, nblk, D, 2 * D, dbeta, dti=0)
-    return dx
+
+
+def layernorm_bwd_drop(dy, s, mean, rstd, gamma, dgamma, dbeta, rows_per_sample, seeds, p, p_path, dres=None):
+    """layernorm_bwd at the s of drop_add_ln_fwd and the residual_dropout backward behind it in one launch -> (ds, dxb):
+    ds the residual stream's gradient (+ dres), dxb = ds * keepE / (1 - p) * keepS / (1 - p_path) the branch's"""
+    rows, D = s.shape
+    nblk = lib.htrvt_layernorm_bwd_blocks(rows)
+    partial = _f32(s, nblk, 2, D)
+    ds, dxb = torch.empty_like(s), torch.empty_like(s)
+    check(lib.htrvt_layernorm_bwd_drop(ptr(dy), ptr(s), ptr(mean), ptr(rstd), ptr(gamma), ptr(dres), ptr(seeds), p, p_path,
+                                       rows_per_sample, ptr(ds), ptr(dxb), ptr(partial), rows, D, dt(s.dtype), stream()),
+          "layernorm_bwd_drop")
+    _ln_param_grads(partial, nblk, D, dgamma, dbeta)
+    return ds, dxb
 
 
 # ---- self-attention, fused (csrc/attention.hip): scores / probabilities stay on chip -----------------------------------
@@ -1118,33 +1150,54 @@ def _put(G, prefix, names, grads):
 FFN_NAMES = ("lin1.weight", "lin1.bias", "lin2.weight", "lin2.bias")
 
 
-def conv_module_fwd(x, P, B, N, eps=1e-5, gn_eps=1e-5, drop=None, save=True):
-    """ConvModule on x [B*N, D]: x + dropout(pointwise_conv2(silu(GroupNorm(dwconv(glu(pointwise_conv1(LayerNorm(x)))))))).
-    drop: None or (seeds, p), seeds an int64 device tensor of two elements (the mask is redrawn from it in the backward) ->
-    (y, (t, mean, rstd, u, c, gn_mean, gn_rstd))"""
-    t, mean, rstd = layernorm_fwd(x, P["layer_norm.weight"], P["layer_norm.bias"], eps, save)
+# The regularisers of a residual site are `(p, p_path, seeds)`: element-wise dropout p on the branch, drop-path p_path on
+# whole samples, seeds an int64 device tensor of two elements (residual_dropout's keys), None when both rates are 0.  A
+# backward takes the forward's.  None stands for a site, or a whole block, without regularisers: the launches without them.
+
+def _site_on(site):
+    return site is not None and (site[0] > 0 or site[1] > 0)
+
+
+def _conv_branch_fwd(t, P, B, N, gn_eps, residual=None):
+    """pointwise_conv2(silu(GroupNorm(dwconv(glu(pointwise_conv1(t)))))) (+ residual, in the last GEMM's epilogue) on the
+    normed rows t -> (o, (u, c, gn_mean, gn_rstd))"""
     u = _pw(t, P["pointwise_conv1.weight"], bias=P["pointwise_conv1.bias"])
     s, gn = gn_mixer_fwd(u, P["depthwise_conv.weight"], P["depthwise_conv.bias"], P["norm.weight"], P["norm.bias"], B, N, gn_eps)
-    if drop is None:
-        y = _pw(s, P["pointwise_conv2.weight"], bias=P["pointwise_conv2.bias"], residual=x)
-    else:
-        y = residual_dropout(_pw(s, P["pointwise_conv2.weight"], bias=P["pointwise_conv2.bias"]), x, N, drop[0], drop[1], 0.0)
-    return y, (t, mean, rstd, u) + gn
+    return _pw(s, P["pointwise_conv2.weight"], bias=P["pointwise_conv2.bias"], residual=residual), (u,) + gn
 
 
-def conv_module_bwd(dy, x, P, saved, B, N, drop=None):
-    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32})"""
-    t, mean, rstd, u, c, gmean, grstd = saved
+def _conv_branch_bwd(do, t, P, saved, B, N):
+    """do [B*N, D], the gradient at the branch's output -> (dt, {the branch's parameter gradients})"""
+    u, c, gmean, grstd = saved
     G = {}
-    do = dy if drop is None else residual_dropout(dy, None, N, drop[0], drop[1], 0.0)
     s = gn_mixer_act(c, gmean, grstd, P["norm.weight"], P["norm.bias"], B, N)
     G["pointwise_conv2.weight"], G["pointwise_conv2.bias"] = _pw_wgrad(do, s)
     du, G["depthwise_conv.weight"], G["depthwise_conv.bias"], G["norm.weight"], G["norm.bias"] = gn_mixer_bwd(
         _pw_dgrad(do, P["pointwise_conv2.weight"]), u, P["depthwise_conv.weight"], P["norm.weight"], P["norm.bias"], B, N,
         (c, gmean, grstd))
     G["pointwise_conv1.weight"], G["pointwise_conv1.bias"] = _pw_wgrad(du, t)
-    dx, G["layer_norm.weight"], G["layer_norm.bias"] = _ln_bwd(_pw_dgrad(du, P["pointwise_conv1.weight"]), x, mean, rstd,
-                                                               P["layer_norm.weight"], dres=dy)
+    return _pw_dgrad(du, P["pointwise_conv1.weight"]), G
+
+
+def conv_module_fwd(x, P, B, N, eps=1e-5, gn_eps=1e-5, drop=None, save=True):
+    """ConvModule on x [B*N, D]: x + drop_path(dropout(pointwise_conv2(silu(GroupNorm(dwconv(glu(pointwise_conv1(
+    LayerNorm(x))))))))).  drop: None or the site's (p, p_path, seeds) ->
+    (y, (t, mean, rstd, u, c, gn_mean, gn_rstd))"""
+    t, mean, rstd = layernorm_fwd(x, P["layer_norm.weight"], P["layer_norm.bias"], eps, save)
+    if not _site_on(drop):
+        y, bs = _conv_branch_fwd(t, P, B, N, gn_eps, residual=x)
+    else:
+        o, bs = _conv_branch_fwd(t, P, B, N, gn_eps)
+        y = residual_dropout(o, x, N, drop[2], drop[0], drop[1])
+    return y, (t, mean, rstd) + bs
+
+
+def conv_module_bwd(dy, x, P, saved, B, N, drop=None):
+    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32})"""
+    t, mean, rstd = saved[:3]
+    do = dy if not _site_on(drop) else residual_dropout(dy, None, N, drop[2], drop[0], drop[1])
+    dt_, G = _conv_branch_bwd(do, t, P, saved[3:], B, N)
+    dx, G["layer_norm.weight"], G["layer_norm.bias"] = _ln_bwd(dt_, x, mean, rstd, P["layer_norm.weight"], dres=dy)
     return dx, G
 
 
@@ -1160,44 +1213,85 @@ def _pad_tokens(x, B, N, Np):
     return xp.view(B * Np, x.shape[1])
 
 
-def plain_attention_fwd(qkv, B, N, h, save=True):
+def plain_attention_pads(dtype, N):
+    """whether the blocks' attention at N tokens takes the unfused route with a padded token count (no dropout there)"""
+    a = 8 if dtype == torch.bfloat16 else 4
+    return not (dtype == torch.bfloat16 and N >= 32) and N % a != 0
+
+
+def plain_attention_fwd(qkv, B, N, h, save=True, drop=None):
     """the blocks' attention -> (a [B*N, D], aux): the fused kernel in bfloat16 with N >= 32 (aux = lse), else the unfused
     GEMM route (aux = P), the parity route; there a token count off the 16-byte row is padded with keys masked by a -1e30
-    score bias (torch copies in and out)"""
+    score bias (torch copies in and out).  drop: (seed, p) on the probabilities, the same mask on the fused and the unfused
+    route; the padded route has another element order and refuses it"""
     if _global_fused(qkv, N):
-        return attention_fwd(qkv, B, N, h, save=save)
+        return attention_fwd(qkv, B, N, h, save=save, drop=drop)
     Np = _padded_tokens(qkv, N)
     if Np == N:
-        return attention_unfused_fwd(qkv, B, N, h)
+        return attention_unfused_fwd(qkv, B, N, h, drop=drop)
+    if drop is not None:
+        raise NotImplementedError(f"attention dropout p = {drop[1]} at N = {N} tokens: the unfused route pads N to {Np} and does "
+                                  "not draw a mask there")
     bias = torch.zeros(h, Np, Np, dtype=torch.float32, device=qkv.device)
     bias[:, :, N:] = -1e30
     out, P = attention_unfused_fwd(_pad_tokens(qkv, B, N, Np), B, Np, h, bias=bias)
     return out.view(B, Np, -1)[:, :N].reshape(B * N, -1), P
 
 
-def plain_attention_bwd(qkv, a, da, aux, B, N, h):
+def plain_attention_bwd(qkv, a, da, aux, B, N, h, drop=None):
     if _global_fused(qkv, N):
-        return attention_bwd(qkv, a, da, aux, B, N, h)
+        return attention_bwd(qkv, a, da, aux, B, N, h, drop=drop)
     Np = _padded_tokens(qkv, N)
     if Np == N:
-        return attention_unfused_bwd(qkv, aux, da, B, N, h)
+        return attention_unfused_bwd(qkv, aux, da, B, N, h, drop=drop)
     dqkv = attention_unfused_bwd(_pad_tokens(qkv, B, N, Np), aux, _pad_tokens(da, B, N, Np), B, Np, h)
     return dqkv.view(B, Np, -1)[:, :N].reshape(B * N, -1)
 
 
 BLOCK_SAVED = 31      # entries of a block's `saved`
+BlockDrop = collections.namedtuple("BlockDrop", "ffn1 attn conv ffn2 probs")
+BlockDrop.__doc__ = """a block's regularisers: the four residual sites' (p, p_path, seeds) in the order of the forward, and
+probs = (seed, p) of the dropout on the attention probabilities or None"""
 
 
-def conformer_block_fwd(x, P, B, N, h, eps=1e-5, conv_eps=1e-5, gn_eps=1e-5, squeeze=False, conv_drop=None, save=True):
+def _block_drops(drops):
+    """None when nothing is active, so that the rate-0 launch sequence runs"""
+    if drops is None or not (any(_site_on(s) for s in drops[:4]) or drops.probs is not None):
+        return None
+    return drops
+
+
+def _add_ln_fwd(branch, res, site, N, gamma, beta, eps, save):
+    """a site in the forward: res + drop_path(dropout(branch)) and the next norm, one launch -> (s, y, mean, rstd)"""
+    p, p_path, seeds = site if site is not None else (0.0, 0.0, None)
+    return drop_add_ln_fwd(branch, res, N, seeds, p, p_path, gamma, beta, eps, save)
+
+
+def _ln_bwd_drop(dy, s, mean, rstd, gamma, site, N, dres=None):
+    """a site in the backward -> (ds, dbranch, dgamma, dbeta)"""
+    p, p_path, seeds = site if site is not None else (0.0, 0.0, None)
+    dgamma, dbeta = torch.zeros_like(gamma), torch.zeros_like(gamma)
+    ds, db = layernorm_bwd_drop(dy, s, mean, rstd, gamma, dgamma, dbeta, N, seeds, p, p_path, dres=dres)
+    return ds, db, dgamma, dbeta
+
+
+def conformer_block_fwd(x, P, B, N, h, eps=1e-5, conv_eps=1e-5, gn_eps=1e-5, squeeze=False, drops=None, save=True):
     """ConformerBlock (squeeze=False) / SqueezeConformerBlock (squeeze=True) on x [B*N, D]:
-    x + 1/2 ffn1 -> + attention -> + the ConvModule's branch -> (SE gate) -> + 1/2 ffn2 -> final_norm -> (y, saved)"""
+    x + 1/2 ffn1 -> + attention -> + the ConvModule's branch -> (SE gate) -> + 1/2 ffn2 -> final_norm -> (y, saved).
+    drops: None or a BlockDrop.  Without an active regulariser every add rides in the epilogue of the GEMM that ends its
+    branch.  With one, that GEMM writes the branch alone (the feed-forwards' 1/2 stays in its alpha: it commutes with the
+    masks) and drop_add_ln_fwd forms the new residual stream and the next norm's output in one launch; behind the SE gate of
+    the squeeze block the conv site is residual_dropout and the plain norm."""
+    drops = _block_drops(drops)
+    if drops is not None:
+        return _conformer_block_fwd_drop(x, P, B, N, h, eps, conv_eps, gn_eps, squeeze, drops, save)
     n1, m1, r1 = layernorm_fwd(x, P["ffn1_norm.weight"], P["ffn1_norm.bias"], eps, save)
     x1, (pre1,) = silu_ffn_fwd(n1, *[P["ffn1." + n] for n in FFN_NAMES], alpha=0.5, residual=x)
     n2, m2, r2 = layernorm_fwd(x1, P["attn_norm.weight"], P["attn_norm.bias"], eps, save)
     qkv = _pw(n2, P["attn.qkv.weight"], bias=P["attn.qkv.bias"])
     a, aux = plain_attention_fwd(qkv, B, N, h, save)
     x2 = _pw(a, P["attn.proj.weight"], bias=P["attn.proj.bias"], residual=x1)
-    x3, cs = conv_module_fwd(x2, _sub(P, "conv_module."), B, N, conv_eps, gn_eps, conv_drop, save)
+    x3, cs = conv_module_fwd(x2, _sub(P, "conv_module."), B, N, conv_eps, gn_eps, None, save)
     x4, ss = x3, (None,) * 4
     if squeeze:
         x4, ss = se_fwd(x3, P["se.fc1.weight"], P["se.fc1.bias"], P["se.fc2.weight"], P["se.fc2.bias"], B, N)
@@ -1208,33 +1302,83 @@ def conformer_block_fwd(x, P, B, N, h, eps=1e-5, conv_eps=1e-5, gn_eps=1e-5, squ
     return y, saved
 
 
-def conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=False, conv_drop=None):
-    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32})"""
+def _conformer_block_fwd_drop(x, P, B, N, h, eps, conv_eps, gn_eps, squeeze, drops, save):
+    """the forward with regularisers; `saved` has the layout of the forward without"""
+    Pc = _sub(P, "conv_module.")
+    n1, m1, r1 = layernorm_fwd(x, P["ffn1_norm.weight"], P["ffn1_norm.bias"], eps, save)
+    b1, (pre1,) = silu_ffn_fwd(n1, *[P["ffn1." + n] for n in FFN_NAMES], alpha=0.5)
+    x1, n2, m2, r2 = _add_ln_fwd(b1, x, drops.ffn1, N, P["attn_norm.weight"], P["attn_norm.bias"], eps, save)
+    qkv = _pw(n2, P["attn.qkv.weight"], bias=P["attn.qkv.bias"])
+    a, aux = plain_attention_fwd(qkv, B, N, h, save, drop=drops.probs)
+    b2 = _pw(a, P["attn.proj.weight"], bias=P["attn.proj.bias"])
+    x2, t, mc, rc = _add_ln_fwd(b2, x1, drops.attn, N, Pc["layer_norm.weight"], Pc["layer_norm.bias"], conv_eps, save)
+    b3, bs = _conv_branch_fwd(t, Pc, B, N, gn_eps)
+    if squeeze:
+        p, p_path, seeds = drops.conv if drops.conv is not None else (0.0, 0.0, None)
+        x3 = residual_dropout(b3, x2, N, seeds, p, p_path)
+        x4, ss = se_fwd(x3, P["se.fc1.weight"], P["se.fc1.bias"], P["se.fc2.weight"], P["se.fc2.bias"], B, N)
+        n5, m5, r5 = layernorm_fwd(x4, P["ffn2_norm.weight"], P["ffn2_norm.bias"], eps, save)
+    else:
+        x3, n5, m5, r5 = _add_ln_fwd(b3, x2, drops.conv, N, P["ffn2_norm.weight"], P["ffn2_norm.bias"], eps, save)
+        x4, ss = x3, (None,) * 4
+    b5, (pre2,) = silu_ffn_fwd(n5, *[P["ffn2." + n] for n in FFN_NAMES], alpha=0.5)
+    x5, y, m6, r6 = _add_ln_fwd(b5, x4, drops.ffn2, N, P["final_norm.weight"], P["final_norm.bias"], eps, save)
+    saved = (n1, m1, r1, pre1, x1, n2, m2, r2, qkv, a, aux, x2, t, mc, rc) + bs + (x3,) + ss + (n5, m5, r5, pre2, x5, m6, r6)
+    return y, saved
+
+
+def conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=False, drops=None):
+    """dy [B*N, D] -> (dx, {parameter gradients by the fork's names, float32}); drops: the forward's"""
+    drops = _block_drops(drops)
     n1, m1, r1, pre1, x1, n2, m2, r2, qkv, a, aux, x2 = saved[:12]
     cs, x3, ss = saved[12:19], saved[19], saved[20:24]
     n5, m5, r5, pre2, x5, m6, r6 = saved[24:]
     G = {}
-    d5, G["final_norm.weight"], G["final_norm.bias"] = _ln_bwd(dy, x5, m6, r6, P["final_norm.weight"])
-    dn5, g = silu_ffn_bwd(d5, n5, P["ffn2.lin1.weight"], P["ffn2.lin2.weight"], (pre2,), 0.5)
+    if drops is None:
+        d5, G["final_norm.weight"], G["final_norm.bias"] = _ln_bwd(dy, x5, m6, r6, P["final_norm.weight"])
+        db5 = d5
+    else:
+        d5, db5, G["final_norm.weight"], G["final_norm.bias"] = _ln_bwd_drop(dy, x5, m6, r6, P["final_norm.weight"], drops.ffn2, N)
+    dn5, g = silu_ffn_bwd(db5, n5, P["ffn2.lin1.weight"], P["ffn2.lin2.weight"], (pre2,), 0.5)
     _put(G, "ffn2.", FFN_NAMES, g)
     if squeeze:
         x4 = torch.empty_like(x3)
         check(lib.htrvt_se_scale_fwd(ptr(x3), ptr(ss[3]), ptr(x4), B, N, x3.shape[1], dt(x3.dtype), stream()), "se_scale_fwd")
     else:
         x4 = x3
-    d4, G["ffn2_norm.weight"], G["ffn2_norm.bias"] = _ln_bwd(dn5, x4, m5, r5, P["ffn2_norm.weight"], dres=d5)
-    d3 = d4
-    if squeeze:
-        d3, g = se_bwd(d4, x3, P["se.fc1.weight"], P["se.fc2.weight"], B, N, ss)
-        _put(G, "se.", ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"), g)
-    d2, gc = conv_module_bwd(d3, x2, _sub(P, "conv_module."), cs, B, N, conv_drop)
+    if drops is None or squeeze:
+        d4, G["ffn2_norm.weight"], G["ffn2_norm.bias"] = _ln_bwd(dn5, x4, m5, r5, P["ffn2_norm.weight"], dres=d5)
+        d3 = d4
+        if squeeze:
+            d3, g = se_bwd(d4, x3, P["se.fc1.weight"], P["se.fc2.weight"], B, N, ss)
+            _put(G, "se.", ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"), g)
+        db3 = d3
+        if drops is not None and _site_on(drops.conv):
+            db3 = residual_dropout(d3, None, N, drops.conv[2], drops.conv[0], drops.conv[1])
+    else:
+        d3, db3, G["ffn2_norm.weight"], G["ffn2_norm.bias"] = _ln_bwd_drop(dn5, x3, m5, r5, P["ffn2_norm.weight"], drops.conv, N,
+                                                                          dres=d5)
+    Pc = _sub(P, "conv_module.")
+    dt_, gc = _conv_branch_bwd(db3, cs[0], Pc, cs[3:], B, N)
+    if drops is None:
+        d2, gc["layer_norm.weight"], gc["layer_norm.bias"] = _ln_bwd(dt_, x2, cs[1], cs[2], Pc["layer_norm.weight"], dres=d3)
+        db2 = d2
+    else:
+        d2, db2, gc["layer_norm.weight"], gc["layer_norm.bias"] = _ln_bwd_drop(dt_, x2, cs[1], cs[2], Pc["layer_norm.weight"],
+                                                                               drops.attn, N, dres=d3)
     _put(G, "conv_module.", gc.keys(), gc.values())
-    G["attn.proj.weight"], G["attn.proj.bias"] = _pw_wgrad(d2, a)
-    dqkv = plain_attention_bwd(qkv, a, _pw_dgrad(d2, P["attn.proj.weight"]), aux, B, N, h)
+    G["attn.proj.weight"], G["attn.proj.bias"] = _pw_wgrad(db2, a)
+    dqkv = plain_attention_bwd(qkv, a, _pw_dgrad(db2, P["attn.proj.weight"]), aux, B, N, h,
+                               drop=drops.probs if drops is not None else None)
     G["attn.qkv.weight"], G["attn.qkv.bias"] = _pw_wgrad(dqkv, n2)
-    d1, G["attn_norm.weight"], G["attn_norm.bias"] = _ln_bwd(_pw_dgrad(dqkv, P["attn.qkv.weight"]), x1, m2, r2,
-                                                             P["attn_norm.weight"], dres=d2)
-    dn1, g = silu_ffn_bwd(d1, n1, P["ffn1.lin1.weight"], P["ffn1.lin2.weight"], (pre1,), 0.5)
+    dn2 = _pw_dgrad(dqkv, P["attn.qkv.weight"])
+    if drops is None:
+        d1, G["attn_norm.weight"], G["attn_norm.bias"] = _ln_bwd(dn2, x1, m2, r2, P["attn_norm.weight"], dres=d2)
+        db1 = d1
+    else:
+        d1, db1, G["attn_norm.weight"], G["attn_norm.bias"] = _ln_bwd_drop(dn2, x1, m2, r2, P["attn_norm.weight"], drops.ffn1, N,
+                                                                           dres=d2)
+    dn1, g = silu_ffn_bwd(db1, n1, P["ffn1.lin1.weight"], P["ffn1.lin2.weight"], (pre1,), 0.5)
     _put(G, "ffn1.", FFN_NAMES, g)
     dx, G["ffn1_norm.weight"], G["ffn1_norm.bias"] = _ln_bwd(dn1, x, m1, r1, P["ffn1_norm.weight"], dres=d1)
     return dx, G
@@ -1244,31 +1388,31 @@ def squeeze_block_fwd(x, P, B, N, h, **kw):
     return conformer_block_fwd(x, P, B, N, h, squeeze=True, **kw)
 
 
-def squeeze_block_bwd(dy, x, P, saved, B, N, h, conv_drop=None):
-    return conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=True, conv_drop=conv_drop)
+def squeeze_block_bwd(dy, x, P, saved, B, N, h, drops=None):
+    return conformer_block_bwd(dy, x, P, saved, B, N, h, squeeze=True, drops=drops)
 
 
-def squeezeformer_fwd(x, P, B, N0, h, d1, d2, conv_drops=None, save=True, **kw):
+def squeezeformer_fwd(x, P, B, N0, h, d1, d2, drops=None, save=True, **kw):
     """SqueezeFormerEncoder on x [B*N0, D]: d1 blocks at N0 tokens, Downsample1D, d2 blocks at N0 // 2, Upsample1D back to N0
-    plus the skip, out_norm -> (y, saved).  conv_drops: per block (stage1 then stage2) None or (seeds, p)"""
-    drops = conv_drops or [None] * (d1 + d2)
+    plus the skip, out_norm -> (y, saved).  drops: per block (stage1 then stage2) None or a BlockDrop"""
+    drops = drops or [None] * (d1 + d2)
     n = N0 // 2 if N0 > 1 else N0
     saved = ()
     for i in range(d1):
-        y, s = squeeze_block_fwd(x, _sub(P, f"stage1.{i}."), B, N0, h, conv_drop=drops[i], save=save, **kw)
+        y, s = squeeze_block_fwd(x, _sub(P, f"stage1.{i}."), B, N0, h, drops=drops[i], save=save, **kw)
         saved, x = saved + (x,) + s, y
     skip, x = x, seq_down2_fwd(x, B, N0)
     for i in range(d2):
-        y, s = squeeze_block_fwd(x, _sub(P, f"stage2.{i}."), B, n, h, conv_drop=drops[d1 + i], save=save, **kw)
+        y, s = squeeze_block_fwd(x, _sub(P, f"stage2.{i}."), B, n, h, drops=drops[d1 + i], save=save, **kw)
         saved, x = saved + (x,) + s, y
     z = seq_up_add_fwd(x, skip, B, n, N0)
     y, mean, rstd = layernorm_fwd(z, P["out_norm.weight"], P["out_norm.bias"], kw.get("eps", 1e-5), save)
     return y, saved + (z, mean, rstd)
 
 
-def squeezeformer_bwd(dy, P, saved, B, N0, h, d1, d2, conv_drops=None):
-    """dy [B*N0, D] -> (dx, {parameter gradients by the fork's names, float32})"""
-    drops = conv_drops or [None] * (d1 + d2)
+def squeezeformer_bwd(dy, P, saved, B, N0, h, d1, d2, drops=None):
+    """dy [B*N0, D] -> (dx, {parameter gradients by the fork's names, float32}); drops: the forward's"""
+    drops = drops or [None] * (d1 + d2)
     n = N0 // 2 if N0 > 1 else N0
     L = BLOCK_SAVED + 1
     z, mean, rstd = saved[-3:]
@@ -1285,3 +1429,5 @@ def squeezeformer_bwd(dy, P, saved, B, N0, h, d1, d2, conv_drops=None):
         d, g = squeeze_block_bwd(d, blk[0], _sub(P, f"stage1.{i}."), blk[1:], B, N0, h, drops[i])
         _put(G, f"stage1.{i}.", g.keys(), g.values())
     return d, G
+
+

@@ -360,6 +360,29 @@ int htrvt_attn_relpos_dropout_bwd(const void* qkv, const float* table, const voi
 int htrvt_residual_dropout(const void* x, const void* res, void* y, int rows_per_sample, int64_t n, int D, const int64_t* seeds,
                            float p, float p_path, int dtype, void* stream);
 
+/* The regularised residual add and the LayerNorm behind it in one launch, forward and backward (csrc/dropnorm.hip): what
+ * htrvt_residual_dropout + htrvt_layernorm_fwd, resp. htrvt_layernorm_bwd + htrvt_residual_dropout, do in two.  x, res, s, y,
+ * dy, dres, ds, dxb [rows][D] (dtype float32 / bfloat16, 16-byte aligned), D as htrvt_layernorm_fwd/_bwd: a multiple of
+ * 4 / 8, at most 1024 / 2048.  The masks and their keys are htrvt_residual_dropout's: keepE by (seeds[0], row * D + col),
+ * keepS by (seeds[1], row / rows_per_sample); the same seeds give the same masks on both routes and in both directions.
+ * htrvt_drop_add_ln_fwd:
+ *     s = res + x * keepE / (1 - p) * keepS / (1 - p_path)         the new residual stream, stored
+ *     y = LayerNorm(s) * gamma + beta, mean / rstd [rows] float32   of s AS STORED (rounded to dtype): (s, mean, rstd) is
+ *                                                                   what htrvt_layernorm_bwd and the backward below take
+ *   mean and rstd may be NULL.
+ * htrvt_layernorm_bwd_drop:
+ *     ds, partial   exactly htrvt_layernorm_bwd(dy, s, mean, rstd, gamma, dres): the gradient of the residual stream (dres
+ *                   may be NULL) and the [htrvt_layernorm_bwd_blocks(rows)][2][D] partial rows of dgamma / dbeta
+ *     dxb = ds * keepE / (1 - p) * keepS / (1 - p_path)             the branch's gradient, from the same registers
+ * Either probability may be 0 (p == 0 skips the per-element hashes); seeds may be NULL when both are.  A probability outside
+ * [0, 1), an unsupported width, a missing or misaligned buffer: an error, nothing is launched. */
+int htrvt_drop_add_ln_fwd(const void* x, const void* res, const int64_t* seeds, float p, float p_path, int rows_per_sample,
+                          const float* gamma, const float* beta, void* s, void* y, float* mean, float* rstd, int64_t rows,
+                          int D, float eps, int dtype, void* stream);
+int htrvt_layernorm_bwd_drop(const void* dy, const void* s, const float* mean, const float* rstd, const float* gamma,
+                             const void* dres, const int64_t* seeds, float p, float p_path, int rows_per_sample, void* ds,
+                             void* dxb, float* partial, int64_t rows, int D, int dtype, void* stream);
+
 /* ---- weight layout helpers ----------------------------------------------------- */
 /* w [Co][Ci][taps] float32 -> fwd [Co][taps][cpad_in], dgrad [Ci][taps][cpad_out] (may be NULL); pads untouched */
 int htrvt_pack_conv_weight(const float* w, void* fwd, void* dgrad, int Co, int Ci, int taps, int cpad_in,
