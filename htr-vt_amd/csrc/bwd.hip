@@ -851,6 +851,11 @@ extern "C" size_t htrvt_colsum_workspace_floats(int64_t rows, int cols) {
 extern "C" int htrvt_colsum(const void* x, int64_t rows, int cols, int64_t ld, float* out, const float* keep, int keep_mod,
                             int dtype, float* workspace, void* stream) {
   const int ch = dtype == HTRVT_BF16 ? 8 : 4;
+  HTRVT_REQUIRE(dtype == HTRVT_BF16 || dtype == HTRVT_F32, "htrvt_colsum: dtype %d is neither float32 nor bfloat16", dtype);
+  HTRVT_REQUIRE(x != nullptr && out != nullptr, "htrvt_colsum: null x / out");
+  HTRVT_REQUIRE(rows >= 0 && rows < (1ll << 32) && cols > 0 && ld >= cols, "htrvt_colsum: %lld rows of %d columns, ld %lld", (long long)rows,
+                cols, (long long)ld);
+  HTRVT_REQUIRE(keep == nullptr || keep_mod >= 1, "htrvt_colsum: a row filter needs keep_mod >= 1 (got %d)", keep_mod);
   HTRVT_REQUIRE(cols % ch == 0 && ld % ch == 0, "htrvt_colsum: cols/ld must be multiples of %d", ch);
   const int gx = (cols / ch + 31) / 32;
   const int splits = colsum_splits(rows);
@@ -865,6 +870,8 @@ extern "C" int htrvt_colsum(const void* x, int64_t rows, int cols, int64_t ld, f
 }
 
 extern "C" int htrvt_rowsum_f32(const float* partial, int rows, int cols, float* out, void* stream) {
+  HTRVT_REQUIRE(partial != nullptr && out != nullptr, "htrvt_rowsum_f32: null partial / out");
+  HTRVT_REQUIRE(rows >= 0 && cols > 0, "htrvt_rowsum_f32: %d rows of %d columns", rows, cols);
   hipLaunchKernelGGL(rowsum_f32_kernel, dim3((cols + RS_NT - 1) / RS_NT), dim3(RS_NT), 0, (hipStream_t)stream, partial, rows, cols, out);
   return check_launch("rowsum_f32");
 }
@@ -997,6 +1004,7 @@ extern "C" int htrvt_conv1_wgrad(const void* img, const float* stats, const void
 
 extern "C" int htrvt_cast_f32(const float* src, void* dst, int64_t n, int dtype, void* stream) {
   HTRVT_REQUIRE(dtype == HTRVT_BF16, "htrvt_cast_f32: only float32 -> bfloat16");
+  HTRVT_REQUIRE(src != nullptr && dst != nullptr && n >= 0, "htrvt_cast_f32: null src / dst or n < 0");
   hipLaunchKernelGGL(cast_kernel<bf16_t>, dim3(grid_for(n)), dim3(NT), 0, (hipStream_t)stream, src, (bf16_t*)dst,
                      (long long)n);
   return check_launch("cast_f32");

@@ -285,6 +285,7 @@ int job_tiles(HtrvtRelayoutJob* j) {
 int launch_one(HtrvtRelayoutJob& j, int dtype, void* stream, const char* what) {
   const int tiles = job_tiles(&j);
   HTRVT_REQUIRE(tiles > 0, "%s: bad arguments", what);
+  HTRVT_REQUIRE(dtype == HTRVT_BF16 || dtype == HTRVT_F32, "%s: dtype %d is neither float32 nor bfloat16", what, dtype);
   j.tile0 = 0;
   if (dtype == HTRVT_BF16)
     hipLaunchKernelGGL(relayout_one_kernel<bf16_t>, dim3(tiles), dim3(NT), 0, (hipStream_t)stream, j);

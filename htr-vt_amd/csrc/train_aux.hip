@@ -141,6 +141,7 @@ extern "C" int htrvt_sumsq_blocks(int64_t n) { return grid_for(n / 4, 1024); }
 
 extern "C" int htrvt_sumsq(const float* x, int64_t n, float* partial, float* out, void* stream) {
   HTRVT_REQUIRE(n > 0 && n % 4 == 0, "htrvt_sumsq: n must be a positive multiple of 4");
+  HTRVT_REQUIRE(x != nullptr && partial != nullptr && out != nullptr, "htrvt_sumsq: null buffer");
   const int nblk = htrvt_sumsq_blocks(n);
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nblk), dim3(NT), 0, (hipStream_t)stream, x, (long long)(n / 4), partial);
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, partial, nblk, out);
@@ -150,6 +151,7 @@ extern "C" int htrvt_sumsq(const float* x, int64_t n, float* partial, float* out
 extern "C" int htrvt_sam_first_step(float* p, const float* g, float* old_p, int64_t n, float rho, const float* norm_sq,
                                     void* stream) {
   HTRVT_REQUIRE(n > 0 && n % 4 == 0 && rho >= 0.f, "htrvt_sam_first_step: n must be a multiple of 4, rho >= 0");
+  HTRVT_REQUIRE(p != nullptr && g != nullptr && old_p != nullptr && norm_sq != nullptr, "htrvt_sam_first_step: null buffer");
   hipLaunchKernelGGL(sam_first_kernel, dim3(grid_for(n / 4)), dim3(NT), 0, (hipStream_t)stream, p, g, old_p,
                      (long long)(n / 4), rho, norm_sq);
   return check_launch("sam_first_step");
@@ -157,6 +159,7 @@ extern "C" int htrvt_sam_first_step(float* p, const float* g, float* old_p, int6
 
 extern "C" int htrvt_sam_restore(float* p, const float* old_p, int64_t n, void* stream) {
   HTRVT_REQUIRE(n > 0 && n % 4 == 0, "htrvt_sam_restore: n must be a multiple of 4");
+  HTRVT_REQUIRE(p != nullptr && old_p != nullptr, "htrvt_sam_restore: null buffer");
   hipLaunchKernelGGL(copy4_kernel, dim3(grid_for(n / 4)), dim3(NT), 0, (hipStream_t)stream, p, old_p, (long long)(n / 4));
   return check_launch("sam_restore");
 }

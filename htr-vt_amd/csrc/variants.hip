@@ -85,6 +85,9 @@ __global__ __launch_bounds__(NT) void relpos_bias_bwd_kernel(const float* __rest
 int check_geo(int N, int P, int window, int shift, int heads, int ldb, WinGeo* g) {
   HTRVT_REQUIRE(N > 0 && P >= N && heads > 0 && ldb >= N, "relpos_bias: need 0 < N <= num_patches, ld >= N (N=%d P=%d ld=%d)", N, P, ldb);
   HTRVT_REQUIRE(window <= 0 || (shift >= 0 && shift < window), "relpos_bias: shift %d outside [0, window %d)", shift, window);
+  // two slots of one window are up to window - 1 apart and the table has the entries -(P - 1) .. P - 1: a wider window indexes
+  // outside it (the reference refuses it as well: a window of ws tokens is a sequence longer than num_patches, HTR_VT.py:35-38)
+  HTRVT_REQUIRE(window <= P, "relpos_bias: window %d wider than num_patches %d (the table has 2 P - 1 entries)", window, P);
   g->N = N;
   g->P = P;
   g->ws = window > 0 ? window : 0;

@@ -307,6 +307,8 @@ int htrvt_conv1_bwd(const void* img, const float* stats, const void* dpool, cons
  * of the window, cyclic shift, 1-D windows, key_padding_mask) as one dense additive score bias [heads][ld][ld] for
  * htrvt_attn_fwd / htrvt_softmax_rows: table entry inside a window, -1e30 outside and in the columns N..ld-1 (sequence
  * padded for the kernels; rows N..ld-1 are don't-care queries).  window <= 0: full attention.
+ * Refused (non-zero, htrvt_last_error(), nothing launched): a null pointer, N > num_patches, ld < N, shift outside [0, window),
+ * window > num_patches (slot distances up to window - 1 would index outside the 2 P - 1 entries; the reference raises too).
  * _bwd: dtable[(2P-1)][heads] = gather-sum of dbias over the (query, key) pairs of each entry, fixed order, overwrites. */
 int htrvt_relpos_bias_fwd(const float* table, float* bias, int N, int num_patches, int window, int shift, int heads, int ld,
                           void* stream);
